@@ -24,7 +24,9 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 LINES, BANDS, SAMPLES = 20000, 425, 598
-HBM_PEAK_GBS = 8000.0            # /opt/skills/guides/MI355X_MICROARCH.md: 8 TB/s spec (6.29 TB/s float4 copy)
+HBM_PEAK_GBS = 8000.0            # MI355X: 8 TB/s spec (6.29 TB/s float4 copy)
+DUMP_BYTES = 56 << 20            # --dump-outputs: budget of the [lines, samples, 4] product sample (64 MB in all)
+DUMP_SEED = 20240
 
 
 def main():
@@ -56,7 +58,14 @@ def main():
     ap.add_argument("--strip-lines", type=int, default=2500, help="lines of the CMF plane the tile scorer measures (e2e / --replicas)")
     ap.add_argument("--in-flight", type=int, default=0,
                     help="flightlines in flight per GPU (srcfinder_amd.inflight); 0 = the default, 3 for every N")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline path computed in its last step as DIR/<name>.npy, "
+                         "float64 (e.g. DIR = bench_outputs); a product over 56 MiB is written as a fixed, seeded row sample")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.replicas:
+        ap.error("--dump-outputs covers the headline path, not --replicas")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves, as a CHILD torch.distributed.run, before
@@ -224,10 +233,13 @@ def main():
                         abs(float(part[okr].sum()) - float(want[0])) <= 1e-9 * max(1.0, abs(float(want[0])))
         pipe.close()
         return {"dt": float(tmax.item()), "t_enq": t_enq, "score_ms": tot_ms.value / max(nlaunch.value, 1),
-                "launches": nlaunch.value, "res": res, "outs": outs, "gather_verified": verified, "placement": placement}
+                "launches": nlaunch.value, "res": res, "outs": outs, "gather_verified": verified, "placement": placement,
+                "gathered": state.get("gathered")}
 
     depth = args.in_flight if args.in_flight > 0 else 3
     main = timed_pass(depth)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, main["res"], main["gathered"] if world > 1 or force_dist else None)
     solo = main if depth == 1 else timed_pass(1)
     res = solo["res"]
 
@@ -898,6 +910,32 @@ def ingest_section(cube, lib, res):
     cmf._Workspace._bufs.clear()
     torch.cuda.empty_cache()
     return sec
+
+
+def dump_outputs(path, res, gathered=None):
+    """--dump-outputs: the last timed step's result as the caller of cmf.robust_mf receives it, one float64 .npy per array.
+    `out` ([lines, ncols, 4]: R, G, B, CMF) is written whole when it fits DUMP_BYTES, otherwise as the rows listed in
+    `out_rows` (a sorted sample drawn with DUMP_SEED: the same rows for the same --lines / --samples).  With N > 1 rank 0
+    also writes the same rows of the gathered [lines, samples] score image; `out` and the per-column arrays are its own shard."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    lines, ncols = res.out.shape[0], res.out.shape[1]
+    row_bytes = res.out[0].numel() * 8 + (gathered[0].numel() * 8 if gathered is not None else 0)
+    nrows = min(lines, DUMP_BYTES // row_bytes)
+    if nrows == lines:
+        rows = np.arange(lines)
+    else:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(lines, nrows, replace=False))
+    idx = torch.as_tensor(rows, device=res.out.device)
+    arrays = {"out": res.out.index_select(0, idx), "out_rows": rows, "colstats": res.colstats, "alphaidx": res.alphaidx,
+              "nuse": res.nuse, "status": res.status}
+    if gathered is not None:
+        arrays["score_image"] = gathered.index_select(0, idx.to(gathered.device))
+    for name, a in arrays.items():
+        a = a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    print("bench.py: %d arrays of the last step written to %s (%d of %d rows of out)" % (len(arrays), path, nrows, lines),
+          file=sys.stderr, flush=True)
 
 
 def flush_c_stdio():
