@@ -276,6 +276,10 @@ int sf_image_dilate_disk(const uint8_t *src, uint8_t *dst, int H, int W, int rad
 size_t sf_image_label8_scratch_bytes(int H, int W);
 int sf_image_label8(const uint8_t *mask, int H, int W, int32_t *labels, int32_t *area, int area_cap, int32_t *ncomp_dev,
                     void *scratch, void *stream);
+/* The same with 4-neighbour connectivity (skimage connectivity=1: remove_small_objects of a boolean image,
+ * srcfinder_util.py:1414-1420, :1453); scratch: sf_image_label8_scratch_bytes(H, W). */
+int sf_image_label4(const uint8_t *mask, int H, int W, int32_t *labels, int32_t *area, int area_cap, int32_t *ncomp_dev,
+                    void *scratch, void *stream);
 /* Clear the pixels of `sel` that lie in components of fewer than minarea pixels (region.area >= mingrowarea, :310). */
 int sf_image_filter_small_components(const int32_t *labels, const int32_t *area, int minarea, uint8_t *sel, int H, int W,
                                      void *stream);
@@ -295,6 +299,36 @@ int sf_masks_compose(const uint8_t *cloud, const uint8_t *spec, const uint8_t *s
 int sf_detect_region_stats(const int32_t *labels, int H, int W, int nregions, const float *sal, const double *cmf,
                            int cmf_nb, int cmf_band, const uint8_t *nodata, double cmfthr, int32_t *bbox, double *rec,
                            void *stream);
+
+/* CMF-threshold plume detector, srcfinder_util.py filtdet :1422-1482 (kde :1383-1387), float64 planes [H][W].
+ * One pass of scipy.ndimage.gaussian_filter(sigma, truncate=1): correlation along `axis` (0: down the columns, 1: along
+ * the rows) with weights[2 * radius + 1] (scipy's _gaussian_kernel1d, uploaded by the caller), mode 'reflect' repeated
+ * when the radius reaches past the line; absin: |src| is filtered.  radius <= 192.  minmax (axis 1 only, optional):
+ * minmax[0..1] = min, max of dst, reduced on the device (scratch: sf_plumes_gauss_scratch_bytes). */
+size_t sf_plumes_gauss_scratch_bytes(int H, int W);
+int sf_plumes_gauss_pass(const double *src, double *dst, int H, int W, int axis, const double *weights, int radius, int absin,
+                         double *minmax, void *scratch, void *stream);
+/* kde weighting and threshold band (:1430-1436): d = (use_abs ? |ch4mf| : ch4mf), times (g - min g) / (max g - min g)
+ * when g is given (minmax from sf_plumes_gauss_pass; g NULL = skip_kde), detkde = clip((d - mfmin) / (mfmax - mfmin), 0, 1);
+ * ch4min = ch4mf >= mfmin, detmask = detkde > 0 (uint8). */
+int sf_plumes_threshold(const double *ch4mf, const double *g, const double *minmax, int H, int W, double mfmin, double mfmax,
+                        int use_abs, double *detkde, uint8_t *ch4min, uint8_t *detmask, void *stream);
+/* Small strong components back (:1455-1463): the pixels of detsmall that detmask lost, labelled 8-connected; every such
+ * component with a pixel of ch4mf >= mfminsmall is set again in detmask. */
+size_t sf_plumes_restore_scratch_bytes(int H, int W);
+int sf_plumes_restore_small(const uint8_t *detsmall, uint8_t *detmask, const double *ch4mf, double mfminsmall, int H, int W,
+                            void *scratch, void *stream);
+/* Compaction (:1466-1477): labels (sf_image_label8 of detmask, count *ncomp_dev) lose the pixels with ch4min == 0 without
+ * re-splitting, are renumbered 1..n' keeping their order (relabel_sequential), and lose the nodata pixels (nodata
+ * optional); detkde (optional) is zeroed on ~ch4min and nodata.  *ncomp_dev = n'. */
+size_t sf_plumes_compact_scratch_bytes(int H, int W);
+int sf_plumes_compact(int32_t *labels, int32_t *ncomp_dev, const uint8_t *ch4min, const uint8_t *nodata, double *detkde, int H,
+                      int W, void *scratch, void *stream);
+/* Plume table over labels 1..ncomp of ch4mf: irec[ncomp + 1][8] int32 = npix, row start, row stop, col start, col stop
+ * (slices), row and col of the max (first in raster order), 0; drec[ncomp + 1][2] float64 = sum, max (row 0 unused).
+ * Deterministic: one workgroup per component sums its pixels in a fixed order.  ime = sum * ime_scale (:1989-1996). */
+int sf_plumes_stats(const int32_t *labels, const double *ch4mf, int H, int W, int ncomp, int32_t *irec, double *drec,
+                    void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * CNN tile scorer (cnn/cnn_pred_pipeline.py + cnn/archs/googlenet1.py, eval graph).  Activations are NHWC

@@ -98,11 +98,20 @@ SIGNATURES = {
     "sf_image_dilate_disk": (i32, [vp, vp, i32, i32, i32, vp, vp]),
     "sf_image_label8_scratch_bytes": (sz, [i32, i32]),
     "sf_image_label8": (i32, [vp, i32, i32, vp, vp, i32, vp, vp, vp]),
+    "sf_image_label4": (i32, [vp, i32, i32, vp, vp, i32, vp, vp, vp]),
     "sf_image_filter_small_components": (i32, [vp, vp, i32, vp, i32, i32, vp]),
     "sf_masks_compose": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]),
     "sf_linalg_det": (i32, [vp, i32, i32, vp, vp, vp]),
     "sf_linalg_inv": (i32, [vp, i32, i32, vp, vp, vp, vp, vp]),
     "sf_detect_region_stats": (i32, [vp, i32, i32, i32, vp, vp, i32, i32, vp, f64, vp, vp, vp]),
+    "sf_plumes_gauss_scratch_bytes": (sz, [i32, i32]),
+    "sf_plumes_gauss_pass": (i32, [vp, vp, i32, i32, i32, vp, i32, i32, vp, vp, vp]),
+    "sf_plumes_threshold": (i32, [vp, vp, vp, i32, i32, f64, f64, i32, vp, vp, vp, vp]),
+    "sf_plumes_restore_scratch_bytes": (sz, [i32, i32]),
+    "sf_plumes_restore_small": (i32, [vp, vp, vp, f64, i32, i32, vp, vp]),
+    "sf_plumes_compact_scratch_bytes": (sz, [i32, i32]),
+    "sf_plumes_compact": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, vp]),
+    "sf_plumes_stats": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
     "sf_cmf_score_timing": (i32, [i32]),
     "sf_debug_set": (i32, [i32, i32]),
     "sf_debug_get": (i32, [i32, C.POINTER(C.c_int)]),

@@ -120,6 +120,8 @@ __global__ __launch_bounds__(256) void k_cc_init(const uint8_t *__restrict__ mas
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < n) lab[i] = mask[i] ? i : -1;
 }
+// CONN 8: the left, upper-left, upper and upper-right neighbours; CONN 4 (skimage connectivity=1): left and upper only
+template <int CONN>
 __global__ __launch_bounds__(256) void k_cc_merge(const uint8_t *__restrict__ mask, int *__restrict__ lab, int H, int W) {
   const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (x >= W || y >= H) return;
@@ -128,8 +130,10 @@ __global__ __launch_bounds__(256) void k_cc_merge(const uint8_t *__restrict__ ma
   if (x > 0 && mask[i - 1]) cc_union(lab, i, i - 1);
   if (y > 0) {
     if (mask[i - W]) cc_union(lab, i, i - W);
-    if (x > 0 && mask[i - W - 1]) cc_union(lab, i, i - W - 1);
-    if (x + 1 < W && mask[i - W + 1]) cc_union(lab, i, i - W + 1);
+    if (CONN == 8) {
+      if (x > 0 && mask[i - W - 1]) cc_union(lab, i, i - W - 1);
+      if (x + 1 < W && mask[i - W + 1]) cc_union(lab, i, i - W + 1);
+    }
   }
 }
 // flatten, mark roots (1 at the first pixel of every component in raster order)
@@ -304,13 +308,14 @@ size_t sf_image_label8_scratch_bytes(int H, int W) {
   const size_t n = (size_t)H * W;
   return 3 * sf_align(n * sizeof(int)) + sf_align(((n + SCAN_B - 1) / SCAN_B + 1) * sizeof(int));
 }
-/* labels[H][W] int32: 0 background, 1..n components of mask != 0 (8-neighbour connectivity) numbered in raster order of
- * their first pixels (skimage.measure.label / scipy.ndimage.label order); area[id] (optional, >= n+1 ints, zeroed here
- * up to area_cap entries); *ncomp_dev receives n. */
-int sf_image_label8(const uint8_t *mask, int H, int W, int32_t *labels, int32_t *area, int area_cap, int32_t *ncomp_dev,
-                    void *scratch, void *stream) {
+}  // extern "C"
+
+namespace {
+template <int CONN>
+int image_label(const char *name, const uint8_t *mask, int H, int W, int32_t *labels, int32_t *area, int area_cap,
+                int32_t *ncomp_dev, void *scratch, void *stream) {
   if (!mask || !labels || !ncomp_dev || !scratch || H < 1 || W < 1 || (size_t)H * W > 0x7fffffffu) {
-    sf_set_error("sf_image_label8: bad argument");
+    sf_set_error("%s: bad argument", name);
     return -1;
   }
   const int n = H * W, nb = sf_cdiv(n, SCAN_B);
@@ -322,7 +327,7 @@ int sf_image_label8(const uint8_t *mask, int H, int W, int32_t *labels, int32_t 
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(k_cc_init, dim3(sf_cdiv(n, 256)), dim3(256), 0, st, mask, lab, n);
   SF_LAUNCH_CHECK("k_cc_init");
-  hipLaunchKernelGGL(k_cc_merge, grid2(W, H), dim3(256), 0, st, mask, lab, H, W);
+  hipLaunchKernelGGL(k_cc_merge<CONN>, grid2(W, H), dim3(256), 0, st, mask, lab, H, W);
   SF_LAUNCH_CHECK("k_cc_merge");
   hipLaunchKernelGGL(k_cc_flatten, dim3(sf_cdiv(n, 256)), dim3(256), 0, st, lab, isroot, n);
   SF_LAUNCH_CHECK("k_cc_flatten");
@@ -336,6 +341,23 @@ int sf_image_label8(const uint8_t *mask, int H, int W, int32_t *labels, int32_t 
   hipLaunchKernelGGL(k_cc_assign, dim3(sf_cdiv(n, 256)), dim3(256), 0, st, lab, rootid, n, labels, area);
   SF_LAUNCH_CHECK("k_cc_assign");
   return 0;
+}
+}  // namespace
+
+extern "C" {
+
+/* labels[H][W] int32: 0 background, 1..n components of mask != 0 (8-neighbour connectivity) numbered in raster order of
+ * their first pixels (skimage.measure.label / scipy.ndimage.label order); area[id] (optional, >= n+1 ints, zeroed here
+ * up to area_cap entries); *ncomp_dev receives n. */
+int sf_image_label8(const uint8_t *mask, int H, int W, int32_t *labels, int32_t *area, int area_cap, int32_t *ncomp_dev,
+                    void *scratch, void *stream) {
+  return image_label<8>("sf_image_label8", mask, H, W, labels, area, area_cap, ncomp_dev, scratch, stream);
+}
+/* The same with 4-neighbour connectivity (skimage connectivity=1, the default of remove_small_objects on a boolean
+ * image); scratch: sf_image_label8_scratch_bytes(H, W). */
+int sf_image_label4(const uint8_t *mask, int H, int W, int32_t *labels, int32_t *area, int area_cap, int32_t *ncomp_dev,
+                    void *scratch, void *stream) {
+  return image_label<4>("sf_image_label4", mask, H, W, labels, area, area_cap, ncomp_dev, scratch, stream);
 }
 
 int sf_image_filter_small_components(const int32_t *labels, const int32_t *area, int minarea, uint8_t *sel, int H, int W,

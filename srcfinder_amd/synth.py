@@ -122,3 +122,22 @@ def make_cube_torch(lines: int, samples: int, nbands: int = NBANDS, *, seed: int
             cube[nodata_lines + 9, a0 - 1 + 10, 2] = -0.25
             cube[nodata_lines + 11, 10, 4] = -1.0
     return cube
+
+
+def make_cmf_plane(lines: int, samples: int, *, seed: int = 1234, nplumes: int = 400, border: int = 8) -> np.ndarray:
+    """A synthetic CMF band [lines, samples] float64 in ppm m for the plume detector: Gaussian noise (sigma 60), nplumes
+    elliptical enhancements of 900-3000 ppm m with radii of 2-12 pixels, and a NODATA (-9999) margin of `border`
+    samples on both sides of every line, as a rotated flight line carries it."""
+    rng = np.random.default_rng(seed)
+    img = rng.normal(0.0, 60.0, (lines, samples))
+    for _ in range(nplumes):
+        cy, cx = int(rng.integers(0, lines)), int(rng.integers(border, samples - border))
+        ry, rx = rng.uniform(2.0, 12.0), rng.uniform(2.0, 12.0)
+        a = rng.uniform(900.0, 3000.0)
+        y0, y1 = max(cy - int(4 * ry), 0), min(cy + int(4 * ry) + 1, lines)
+        x0, x1 = max(cx - int(4 * rx), 0), min(cx + int(4 * rx) + 1, samples)
+        yy, xx = np.mgrid[y0:y1, x0:x1]
+        img[y0:y1, x0:x1] += a * np.exp(-(((yy - cy) / ry) ** 2 + ((xx - cx) / rx) ** 2))
+    img[:, :border] = -9999.0
+    img[:, samples - border:] = -9999.0
+    return img
