@@ -288,8 +288,7 @@ int sf_cmf_run(const float *cube, int lines, int bands, int samples, int s0, int
       return rc;
     // det() at the edge of the float64 range (a column of fewer valid rows than bands): the finite grid points next to a lost
     // one are factorised for real, robust_mf.py:111-113 (linalg.hip; nine small launches that find nothing to do otherwise)
-    if (sf_tune().det_variant != 2 &&
-        (rc = sf_launch_exact_det(w.cov, nuse, status, alphas, g, SF_NARROW_DET_WINDOW, nullptr, nll, alphaidx, w.scratch, st)))
+    if ((rc = sf_launch_exact_det(w.cov, nuse, status, alphas, g, SF_NARROW_DET_WINDOW, nullptr, nll, alphaidx, w.scratch, st)))
       return rc;
   }
   if ((rc = sf_launch_filter(w.mu, w.d, w.lam, w.evec, alphas, alphaidx, abscf, reflectance, g, status, w.filt, w.bias, st)))
@@ -305,29 +304,38 @@ static int *sf_tune_slot(int key) {
     case 1: return &t.score_variant;
     case 2: return &t.score_lpw;
     case 3: return &t.score_xcd;
-    case 4: return &t.sweep_variant;
-    case 5: return &t.cov_variant;
     case 6: return &t.extract_variant;
     case 7: return &t.eigh_lpp;
-    case 8: return &t.sweep4r_waves;
     case 10: return &t.wide_eigh_variant;
     case 14: return &t.lu_variant;
     case 15: return &t.det_variant;
     case 16: return &t.cnn_variant;
     case 17: return &t.cnn_conv_variant;
     case 18: return &t.cnn_pool_variant;
-    case 19: return &t.extract_nt;
     case 20: return &t.sweep4_form;
     case 21: return &t.sweep_grid;
     case 22: return &t.wjac_stamps;
     case 24: return &t.wsweep_variant;
-    case 26: return &t.det_slots;
     default: return nullptr;
+  }
+}
+// the values a key takes where some of its forms are retired (a retired value would silently run the default: an A/B run would
+// measure the same code twice); the other keys take any value they did
+static bool sf_tune_value_ok(int key, int v) {
+  switch (key) {
+    case 2: return v >= 0;                                     // lines per workgroup (0: the built-in choice)
+    case 6: case 15: return v == 0 || v == 1;
+    case 7: return v == 0 || v == 2;
+    case 16: return v == 0 || v == 1 || v == 3;
+    case 17: return v == 0 || v == 1 || v == 2 || v == 4;
+    case 20: return v == 0 || v == 1 || v == 4 || v == 5;
+    default: return true;
   }
 }
 int sf_debug_set(int key, int value) {
   int *slot = sf_tune_slot(key);
   if (!slot) { sf_set_error("sf_debug_set: unknown key %d", key); return -1; }
+  if (!sf_tune_value_ok(key, value)) { sf_set_error("sf_debug_set: key %d has no form %d", key, value); return -1; }
   *slot = value;
   return 0;
 }

@@ -414,27 +414,21 @@ int sf_launch_eigh_unit(const double *cov, const int32_t *nuse, const SfGeom &g,
 static int launch_eigh(const double *cov, const int32_t *nuse, const SfGeom &g, double *d, double *lam, double *evec,
                        int32_t *status, void *scratch, int unit, hipStream_t st) {
   const int p2 = g.p + (g.p & 1);
-  // Lanes per column pair: 8 is the measured optimum (tools/probe_eigh.py, one 72x72 matrix: 8 lanes 0.65 ms,
-  // 4 lanes -- 3 waves, one per SIMD, twice the rows per lane -- 0.78 ms, 16 lanes -- 9 waves -- 0.77 ms).
-  // The other two stay reachable through sf_debug_set(7, .) for the production sizes.
-  const int lpp = (sf_tune().eigh_lpp == 4 || sf_tune().eigh_lpp == 8 || sf_tune().eigh_lpp == 16) ? sf_tune().eigh_lpp : 8;
-  const bool lpp4 = lpp == 4 && (p2 == 72 || p2 == 84);
-  const bool lpp16 = lpp == 16 && (p2 == 72 || p2 == 84);
+  // Lanes per column pair: 8, the measured optimum (one 72x72 matrix: 8 lanes 0.65 ms, 4 lanes -- 3 waves, one per SIMD,
+  // twice the rows per lane -- 0.78 ms, 16 lanes -- 9 waves -- 0.77 ms).
   int LD = p2;
-  if (lpp4) { while ((LD % 32) != 12 && (LD % 32) != 20) ++LD; }     // 4 consecutive columns x 4 rows: 64 distinct banks
-  else if (lpp16) { while ((LD % 32) != 16) ++LD; }
-  else { while ((LD % 32) != 8 && (LD % 32) != 24) ++LD; }
+  while ((LD % 32) != 8 && (LD % 32) != 24) ++LD;
   // The tridiagonal preconditioner (cmf_eigh_pre.h; the CH4 / CO2 window sizes, 8 lanes per pair) is built, correct and OFF by
   // default: sf_debug_set(7, 2) turns it on.  Measured (profiles/r06_eigh_precond.md): one sweep instead of nine, but the
   // preconditioner itself costs 1.34 M cycles of latency-bound float64 work on ONE workgroup (0.62 against 0.66 ms for a 72-band
   // matrix alone) and its second LDS matrix leaves one workgroup per CU instead of three (598 columns: 1.90 against 1.14 ms).
-  const bool pre = !lpp4 && !lpp16 && (p2 == 72 || p2 == 84) && sf_tune().eigh_lpp == 2;
+  const bool pre = (p2 == 72 || p2 == 84) && sf_tune().eigh_lpp == 2;
   const size_t lds = ((size_t)p2 * LD + 2 * p2 + (pre ? (size_t)p2 * LD + 8 * p2 + 16 : 0)) * sizeof(double);
   if (lds > 160 * 1024 - 64 || g.p > SF_MAX_ACTIVE_FUSED) {
     sf_set_error("active window of %d bands exceeds the LDS-resident eigensolver (max %d)", g.p, SF_MAX_ACTIVE_FUSED);
     return -2;
   }
-  int threads = (p2 / 2) * (lpp4 ? 4 : (lpp16 ? 16 : 8));
+  int threads = (p2 / 2) * 8;
   threads = (threads + 63) / 64 * 64;
   if (threads < 64) threads = 64;
   if (pre) threads = 4 * p2;                    // exactly four lanes per column (cmf_eigh_pre.h; __launch_bounds__ of the instantiation)
@@ -450,10 +444,6 @@ static int launch_eigh(const double *cov, const int32_t *nuse, const SfGeom &g, 
   int rc = -2;
   if (pre) {
     rc = (p2 == 72) ? go(k_eigh<9, true, 8, 72>) : go(k_eigh<11, false, 8, 84>);
-  } else if (lpp4) {
-    rc = (p2 == 72) ? go(k_eigh<18, true, 4>) : go(k_eigh<21, true, 4>);
-  } else if (lpp16) {
-    rc = (p2 == 72) ? go(k_eigh<5, false, 16>) : go(k_eigh<6, false, 16>);
   } else {
   switch (rmax) {
 #define EIG_CASE(R) case R: rc = full ? go(k_eigh<R, true, 8>) : go(k_eigh<R, false, 8>); break;

@@ -334,17 +334,7 @@ __global__ __launch_bounds__(256, 2) void k_extract_pipe(const float *__restrict
                                                           double *__restrict__ sum_part, int *__restrict__ cnt_part) {
   extract_pipe_body<TL, P, NTS>(cube, L, B, C, s0, Cs, b0, PS, xt, mask_t, lines_per_wg, cs, ncb, nchunk, sum_part, cnt_part);
 }
-// the wide windows: ONE line per tile, one wave per SIMD (the whole register file: 107 row loads in flight and 107 float64
-// column sums per lane)
-template <int P>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
-void k_extract_wide(const float *__restrict__ cube, int L, int B, int C, int s0, int Cs, int b0, int PS, float *__restrict__ xt,
-                    uint8_t *__restrict__ mask_t, int lines_per_wg, int cs, int ncb, int nchunk, double *__restrict__ sum_part,
-                    int *__restrict__ cnt_part) {
-  extract_pipe_body<1, P, true>(cube, L, B, C, s0, Cs, b0, PS, xt, mask_t, lines_per_wg, cs, ncb, nchunk, sum_part, cnt_part);
-}
-
-// the same with EIGHT waves (two per SIMD, half the rows and half the sums each: round 6; the default)
+// the wide windows: ONE line per tile, EIGHT waves (two per SIMD, half the rows and half the float64 column sums each: round 6)
 template <int P>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void k_extract_wide8(const float *__restrict__ cube, int L, int B, int C, int s0, int Cs, int b0, int PS, float *__restrict__ xt,
@@ -612,55 +602,44 @@ int sf_launch_extract(const float *cube, int lines, int bands, int samples, int 
                          fuse ? sum_part : nullptr, fuse ? cnt_part : nullptr);
       return 0;
     };
-    // 16-byte pieces where a window row is a whole number of them (p = 72: 5400 floats at 75 columns); knob 6 = 7 keeps the 4-byte form
-    const bool v4 = ((p * ncols) & 3) == 0 && sf_tune().extract_variant != 7;
+    // 16-byte pieces where a window row is a whole number of them (p = 72: 5400 floats at 75 columns)
+    const bool v4 = ((p * ncols) & 3) == 0;
     const int rc = v4 ? flat(k_extract_flat<1024, 6, 6, true>, 4096, 6, 1024) : flat(k_extract_flat<1024, 12, 6>, 1024, 12, 1024);
     if (rc) return rc;
     SF_LAUNCH_CHECK("k_extract_flat");
     return 0;
   }
   const int ncb = sf_cdiv(ncols, 64);
-  if (fuse && (sf_tune().extract_variant == 0 || sf_tune().extract_variant == 3) && p == 72) {
+  if (fuse && p == 72 && sf_tune().extract_variant == 0) {
     // the production window: software-pipelined kernel, FOUR lines per tile (72 row loads in flight per wave, 74 KB of
     // LDS, two workgroups per CU: 147 KB of loads in flight per CU against 110 KB with two-line tiles at three
-    // workgroups -- 10.45 / 10.40 against 10.64 / 10.48 ms per flightline, same box, same bits; tools/tune_extract.py)
-    const int tl = sf_tune().extract_variant == 3 ? 3 : 4, csx = (tl * 72) | 1;
+    // workgroups -- 10.45 / 10.40 against 10.64 / 10.48 ms per flightline, same box, same bits), non-temporal xt stores
+    // (3.4 GB, re-read only after the whole pass): -0.08 ms alone, same bits
+    const int csx = (4 * 72) | 1;
     const size_t ldsx = (size_t)64 * csx * sizeof(float);
-    if (tl == 3) {
-      if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_extract_pipe<3, 72>), ldsx)) return rc;
-      hipLaunchKernelGGL((k_extract_pipe<3, 72>), dim3(sf_xcd_grid(ncb, nchunk)), dim3(256), ldsx, st, cube, lines, bands, samples,
-                         s0, ncols, b0, PS, xt, mask_t, lpw, csx, ncb, nchunk, sum_part, cnt_part);
-    } else if (!sf_tune().extract_nt) {     // non-temporal xt stores (3.4 GB, re-read only after the whole pass): -0.08 ms alone, same bits
-      if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_extract_pipe<4, 72, true>), ldsx)) return rc;
-      hipLaunchKernelGGL((k_extract_pipe<4, 72, true>), dim3(sf_xcd_grid(ncb, nchunk)), dim3(256), ldsx, st, cube, lines, bands, samples,
-                         s0, ncols, b0, PS, xt, mask_t, lpw, csx, ncb, nchunk, sum_part, cnt_part);
-    } else {
-      if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_extract_pipe<4, 72>), ldsx)) return rc;
-      hipLaunchKernelGGL((k_extract_pipe<4, 72>), dim3(sf_xcd_grid(ncb, nchunk)), dim3(256), ldsx, st, cube, lines, bands, samples,
-                         s0, ncols, b0, PS, xt, mask_t, lpw, csx, ncb, nchunk, sum_part, cnt_part);
-    }
-  } else if (fuse && (sf_tune().extract_variant == 0 || sf_tune().extract_variant == 9) && (p == 425 || p == 416)) {
+    if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_extract_pipe<4, 72, true>), ldsx)) return rc;
+    hipLaunchKernelGGL((k_extract_pipe<4, 72, true>), dim3(sf_xcd_grid(ncb, nchunk)), dim3(256), ldsx, st, cube, lines, bands, samples,
+                       s0, ncols, b0, PS, xt, mask_t, lpw, csx, ncb, nchunk, sum_part, cnt_part);
+  } else if (fuse && p == 72) {     // sf_debug_set(6, 1): two lines per tile, round 1's form
+    if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_extract_pipe<TL, 72>), maxlds)) return rc;
+    hipLaunchKernelGGL((k_extract_pipe<TL, 72>), dim3(sf_xcd_grid(ncb, nchunk)), dim3(256), lds, st, cube, lines, bands, samples,
+                       s0, ncols, b0, PS, xt, mask_t, lpw, cs, ncb, nchunk, sum_part, cnt_part);
+  } else if (fuse && sf_tune().extract_variant == 0 && (p == 425 || p == 416)) {
     // the full-band window of the benchmark (1..425) and the reference's -R window (5..420: robust_mf.py:186-187): ONE line per
-    // tile (64 columns x p bands = 109 KB of LDS, one workgroup per CU with the whole register file: 107 row loads in flight
-    // and 107 float64 column sums per lane), the column sums fused as on the narrow windows -- round 4 ran the blocked kernel
-    // (2.7 TB/s) and re-read the 20.5 GB of xt for the sums (k_colsum)
+    // tile (64 columns x p bands = 109 KB of LDS, one workgroup per CU), the column sums fused as on the narrow windows -- round 4
+    // ran the blocked kernel (2.7 TB/s) and re-read the 20.5 GB of xt for the sums (k_colsum); round 6: eight waves (two per SIMD,
+    // half the rows and half the float64 sums each: 196 registers) -- 14.6 -> ~10 ms a flightline at p = 425 (the full-band step
+    // 274.4 -> 270.1 ms), the same bits as the four-wave form
     const int csx = p | 1;
     const size_t ldsx = (size_t)64 * csx * sizeof(float);
-    // round 6: EIGHT waves (two per SIMD, half the rows and half the float64 sums each: 196 registers) -- 14.6 -> ~10 ms a
-    // flightline at p = 425 (the full-band step 274.4 -> 270.1 ms), the same bits; sf_debug_set(6, 9): the four-wave form
-    const bool w4 = sf_tune().extract_variant == 9;
-#define SF_WIDE_GO(K)                                                                                                             \
-  {                                                                                                                               \
-    if (int rc = sf_lds_attr(reinterpret_cast<const void *>(K), ldsx)) return rc;                                                 \
-    hipLaunchKernelGGL((K), dim3(sf_xcd_grid(ncb, nchunk)), dim3(w4 ? 256 : 512), ldsx, st, cube, lines, bands, samples, s0, ncols, \
-                       b0, PS, xt, mask_t, lpw, csx, ncb, nchunk, sum_part, cnt_part);                                            \
-  }
-    if (p == 425) {
-      if (w4) SF_WIDE_GO(k_extract_wide<425>) else SF_WIDE_GO(k_extract_wide8<425>)
-    } else {
-      if (w4) SF_WIDE_GO(k_extract_wide<416>) else SF_WIDE_GO(k_extract_wide8<416>)
-    }
-#undef SF_WIDE_GO
+    const void *kern = p == 425 ? reinterpret_cast<const void *>(k_extract_wide8<425>) : reinterpret_cast<const void *>(k_extract_wide8<416>);
+    if (int rc = sf_lds_attr(kern, ldsx)) return rc;
+    if (p == 425)
+      hipLaunchKernelGGL((k_extract_wide8<425>), dim3(sf_xcd_grid(ncb, nchunk)), dim3(512), ldsx, st, cube, lines, bands, samples, s0,
+                         ncols, b0, PS, xt, mask_t, lpw, csx, ncb, nchunk, sum_part, cnt_part);
+    else
+      hipLaunchKernelGGL((k_extract_wide8<416>), dim3(sf_xcd_grid(ncb, nchunk)), dim3(512), ldsx, st, cube, lines, bands, samples, s0,
+                         ncols, b0, PS, xt, mask_t, lpw, csx, ncb, nchunk, sum_part, cnt_part);
   } else if (fuse && sf_tune().extract_variant == 0 && p == 83) {
     // the CO2 window (robust_mf.py:190-191): the same kernel, three lines per tile (64 KB of LDS: two workgroups per CU;
     // four lines would be 85 KB and one), rows padded to 84 floats, non-temporal stores
@@ -669,10 +648,6 @@ int sf_launch_extract(const float *cube, int lines, int bands, int samples, int 
     if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_extract_pipe<3, 83, true>), ldsx)) return rc;
     hipLaunchKernelGGL((k_extract_pipe<3, 83, true>), dim3(sf_xcd_grid(ncb, nchunk)), dim3(256), ldsx, st, cube, lines, bands, samples,
                        s0, ncols, b0, PS, xt, mask_t, lpw, csx, ncb, nchunk, sum_part, cnt_part);
-  } else if (fuse && sf_tune().extract_variant != 2 && p == 72) {     // variant 5 (any other value): two lines per tile, round 1's form
-    if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_extract_pipe<TL, 72>), maxlds)) return rc;
-    hipLaunchKernelGGL((k_extract_pipe<TL, 72>), dim3(sf_xcd_grid(ncb, nchunk)), dim3(256), lds, st, cube, lines, bands, samples,
-                       s0, ncols, b0, PS, xt, mask_t, lpw, cs, ncb, nchunk, sum_part, cnt_part);
   } else if (fuse && p <= XT_PBMAX)
     hipLaunchKernelGGL((k_extract<TL, true>), dim3(sf_xcd_grid(ncb, nchunk)), dim3(256), lds, st, cube, lines, bands,
                        samples, s0, ncols, b0, p, PS, xt, mask_t, lpw, pbmax, cs, ncb, nchunk, sum_part, cnt_part);
@@ -690,7 +665,7 @@ size_t sf_extract_sum_bytes(const SfGeom &g) {
   return sf_align((size_t)nchunk * g.ncols * g.ps * sizeof(double)) + sf_align((size_t)nchunk * g.ncols * sizeof(int));
 }
 bool sf_extract_fuses_sum(int p) {
-  return p <= XT_PBMAX || ((p == 425 || p == 416) && (sf_tune().extract_variant == 0 || sf_tune().extract_variant == 9));
+  return p <= XT_PBMAX || ((p == 425 || p == 416) && sf_tune().extract_variant == 0);
 }
 
 int sf_launch_extract_fused(const float *cube, int lines, int bands, int samples, int s0, int b0, const SfGeom &g,

@@ -430,7 +430,7 @@ int sf_launch_nll_finish(const double *part, int nsplit, const int32_t *nuse, co
 }
 
 static bool sweep4_ok(const SfGeom &g, int xt_f64) {
-  return !xt_f64 && sf_tune().sweep_variant != 1 && g.nu == SF_SW4_NM && sf_sw4_groups(g.p) != 0;
+  return !xt_f64 && g.nu == SF_SW4_NM && sf_sw4_groups(g.p) != 0;
 }
 
 // per column: the W fragments of the 16x16x4 sweep ([nt][s4][64]) or of the 4x4x4 sweeps ([nj][nje][16], nje = nj rounded up
@@ -479,8 +479,7 @@ int sf_launch_loocv(const void *xt, int xt_f64, const uint8_t *mask_t, const int
         return rc;
       return launch_nll(part, nsplit, nuse, d, lam, status, alphas, g, 1, nll, alphaidx, st, nullptr, lrok);
     }
-    int rc4 = sf_launch_sweep4((const float *)xt, mask_t, nuse, mu, lam, wfrag, wstride, status, alphas, g, nsplit, part,
-                               sf_tune().sweep_variant, sf_tune().sweep_variant == 2 ? nullptr : lr, st);
+    int rc4 = sf_launch_sweep4((const float *)xt, mask_t, nuse, mu, lam, wfrag, wstride, status, alphas, g, nsplit, part, 0, lr, st);
     if (rc4) return rc4;
     return launch_nll(part, nsplit, nuse, d, lam, status, alphas, g, 1, nll, alphaidx, st);
   }

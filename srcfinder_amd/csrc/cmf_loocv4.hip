@@ -83,7 +83,6 @@ __device__ __forceinline__ void lds_wait6(double &a, double &b, double &c, doubl
   else asm volatile("s_waitcnt lgkmcnt(%6)" : "+a"(a), "+a"(b), "+a"(c), "+a"(d), "+a"(e), "+a"(f) : "n"(CNT));
 }
 
-template <int EXP>  // 0 = production; 1..3 = timing experiments (skip GEMM1 / epilogue / GEMM2), wrong results
 __global__ __launch_bounds__(256, 1) void k_sweep4(const float *__restrict__ xt, const uint8_t *__restrict__ mask_t,
                                                     const int32_t *__restrict__ nuse, const double *__restrict__ mu,
                                                     const double *__restrict__ lam, const double *__restrict__ wfrag,
@@ -171,7 +170,6 @@ __global__ __launch_bounds__(256, 1) void k_sweep4(const float *__restrict__ xt,
   if (tid < NJ) zeros4[tid] = 0.0;
   __syncthreads();
 
-  if (EXP == 4) r0 = rend;   // timing experiment: prologue + final reduction only
   for (; r0 < rend; r0 += 16 * 4) {
     const bool rowok = rowok_next;
     nrowok += (rowok && g == 0) ? 1 : 0;
@@ -203,10 +201,6 @@ __global__ __launch_bounds__(256, 1) void k_sweep4(const float *__restrict__ xt,
       z[0][jg] = 0.0;
       wa[0][jg] = lds_ld<jg * 128>(wadr);
     });
-    if constexpr (EXP == 1) {
-#pragma unroll
-      for (int jg = 0; jg < NJ; ++jg) z[0][jg] = x[jg] + wa[0][jg];
-    } else
     static_for<0, NJ>([&](auto sc) {
       constexpr int s = decltype(sc)::value;
       static_for<0, NJ / 6>([&](auto kc) {
@@ -248,10 +242,6 @@ __global__ __launch_bounds__(256, 1) void k_sweep4(const float *__restrict__ xt,
         if constexpr (gr * TG + k < NM) br[k][t % DEPTH] = lds_ld<(k * NJ + jg) * 512>(cadr + gr * (TG * NJ * 512));
       });
     };
-    if constexpr (EXP == 3) {
-#pragma unroll
-      for (int u = 0; u < NM; ++u) N[u] += z[u & 3][u];
-    } else {
     static_for<0, DEPTH - 1>(loadb);
     double acc[2][TG][4];
     // Row reduction of the TG alpha tiles of group `gr` from accumulator set `st`, in four short stages of
@@ -265,9 +255,7 @@ __global__ __launch_bounds__(256, 1) void k_sweep4(const float *__restrict__ xt,
       for (int k = 0; k < ntile; ++k) {
         const int u = gq * TG + k;
         // acc[st][k][s] = q for alpha i = 16u + li and row (group (m + s) % 4, index g) of this tile
-        if constexpr (EXP == 2) {
-          if (stage == 0) N[u] += (acc[st][k][0] + acc[st][k][1]) + (acc[st][k][2] + acc[st][k][3]);
-        } else if constexpr (stage == 0) {
+        if constexpr (stage == 0) {
           const double q0 = acc[st][k][0], q1 = acc[st][k][1], q2 = acc[st][k][2], q3 = acc[st][k][3];
           rm01[k] = q0 * q1; rm23[k] = q2 * q3; rs01[k] = q0 + q1; rs23[k] = q2 + q3;
           sg[u] |= __double2hiint(q0) | __double2hiint(q1) | __double2hiint(q2) | __double2hiint(q3);   // any q < 0 so far
@@ -315,7 +303,6 @@ __global__ __launch_bounds__(256, 1) void k_sweep4(const float *__restrict__ xt,
         });
       }
     });
-    }
     ntile += 1;
   }
 
@@ -374,7 +361,7 @@ __global__ __launch_bounds__(256, 1) void k_sweep4(const float *__restrict__ xt,
 // NW waves per workgroup share the LDS tables: with NW = 8 every SIMD holds two waves of the same workgroup and
 // one wave's LDS reads, DPP moves and waits run under the other's MFMAs (the tables allow only one workgroup per
 // CU, and with a single wave per SIMD every non-MFMA instruction is a bubble in the matrix pipe).
-template <int EXP, int NW, int NK>   // NK = rank / 4: 7 (rank 28, lrok == 1) or 9 (rank 36, lrok == 2)
+template <int NW, int NK>   // NK = rank / 4: 7 (rank 28, lrok == 1) or 9 (rank 36, lrok == 2)
 __global__ __launch_bounds__(64 * NW, 1) void k_sweep4r(const float *__restrict__ xt, const uint8_t *__restrict__ mask_t,
                                                     const int32_t *__restrict__ nuse, const double *__restrict__ mu,
                                                     const double *__restrict__ ufrag_g, const double *__restrict__ wfrag2_g,
@@ -459,7 +446,6 @@ __global__ __launch_bounds__(64 * NW, 1) void k_sweep4r(const float *__restrict_
   int r0 = rbeg + 16 * wave;
   if (r0 < rend) fetch(r0, xraw, rowok_next);
 
-  if (EXP == 4) r0 = rend;   // timing experiment: prologue + final reduction only
   for (; r0 < rend; r0 += 16 * NW) {
     const bool rowok = rowok_next;
     nrowok += (rowok && g == 0) ? 1 : 0;
@@ -486,10 +472,6 @@ __global__ __launch_bounds__(64 * NW, 1) void k_sweep4r(const float *__restrict_
       z[0][jg] = 0.0;
       wa[0][jg] = lds_ld<jg * 128, VG>(wadr);
     });
-    if constexpr (EXP == 1) {
-#pragma unroll
-      for (int jg = 0; jg < NJ; ++jg) z[0][jg] = x[jg] + wa[0][jg];
-    } else
     static_for<0, NJ>([&](auto sc) {
       constexpr int s = decltype(sc)::value;
       static_for<0, NJ / 6>([&](auto kc) {
@@ -550,10 +532,6 @@ __global__ __launch_bounds__(64 * NW, 1) void k_sweep4r(const float *__restrict_
         if constexpr (gr * TG + k < NM) br[k][t % DEPTH] = lds_ld<(k * NK + jg) * 512, VG>(cadr + gr * (TG * NK * 512));
       });
     };
-    if constexpr (EXP == 3) {
-#pragma unroll
-      for (int u = 0; u < NM; ++u) N[u] += t4[u & 3][u % NK];
-    } else {
     static_for<0, DEPTH - 1>(loadb);
     double acc[2][TG][4];
     // Row reduction of the TG alpha tiles of group `gr` from accumulator set `st`, in four short stages of
@@ -567,9 +545,7 @@ __global__ __launch_bounds__(64 * NW, 1) void k_sweep4r(const float *__restrict_
       for (int k = 0; k < ntile; ++k) {
         const int u = gq * TG + k;
         // acc[st][k][s] = q for alpha i = 16u + li and row (group (m + s) % 4, index g) of this tile
-        if constexpr (EXP == 2) {
-          if (stage == 0) N[u] += (acc[st][k][0] + acc[st][k][1]) + (acc[st][k][2] + acc[st][k][3]);
-        } else if constexpr (stage == 0) {
+        if constexpr (stage == 0) {
           const double q0 = acc[st][k][0], q1 = acc[st][k][1], q2 = acc[st][k][2], q3 = acc[st][k][3];
           rm01[k] = q0 * q1; rm23[k] = q2 * q3; rs01[k] = q0 + q1; rs23[k] = q2 + q3;
           sg[u] |= __double2hiint(q0) | __double2hiint(q1) | __double2hiint(q2) | __double2hiint(q3);   // any q < 0 so far
@@ -622,7 +598,6 @@ __global__ __launch_bounds__(64 * NW, 1) void k_sweep4r(const float *__restrict_
         });
       }
     });
-    }
     ntile += 1;
   }
 
@@ -680,14 +655,13 @@ __global__ __launch_bounds__(64 * NW, 1) void k_sweep4r(const float *__restrict_
 constexpr size_t sw4r_lds(int nk) { return ((size_t)S4M * nk * 64 + S4J * S4J * 16 + S4J * nk * 16 + 4 * S4J) * sizeof(double); }
 constexpr size_t SW4_LDS = ((size_t)S4M * S4J * 64 + S4J * S4J * 16 + 4 * S4J + S4J) * sizeof(double);   // c fragments, W blocks, mean, 18 zeros
 
-template <int EXP>
-int launch_sweep4_t(const float *xt, const uint8_t *mask_t, const int32_t *nuse, const double *mu, const double *lam,
-                    const double *wfrag, size_t wstride, const int32_t *status, const double *alphas, const SfGeom &g,
-                    int nsplit, double *part, hipStream_t st, const int32_t *lrok = nullptr) {
-  if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_sweep4<EXP>), SW4_LDS)) return rc;
+int launch_sweep4(const float *xt, const uint8_t *mask_t, const int32_t *nuse, const double *mu, const double *lam,
+                  const double *wfrag, size_t wstride, const int32_t *status, const double *alphas, const SfGeom &g,
+                  int nsplit, double *part, hipStream_t st, const int32_t *lrok) {
+  if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_sweep4), SW4_LDS)) return rc;
   int rows = sf_cdiv(g.lines, nsplit);
   rows = (rows + 63) / 64 * 64;
-  hipLaunchKernelGGL(k_sweep4<EXP>, dim3(g.ncols, nsplit), dim3(256), SW4_LDS, st, xt, mask_t, nuse, mu, lam, wfrag,
+  hipLaunchKernelGGL(k_sweep4, dim3(g.ncols, nsplit), dim3(256), SW4_LDS, st, xt, mask_t, nuse, mu, lam, wfrag,
                      wstride, status, alphas, g.nalpha, g.lines, g.p, g.ps, rows, part, lrok);
   SF_LAUNCH_CHECK("k_sweep4");
   return 0;
@@ -697,9 +671,6 @@ int launch_sweep4r(const float *xt, const uint8_t *mask_t, const int32_t *nuse, 
                    const double *wfrag2, const int32_t *lrok, const double *lam, const double *wfrag, size_t wstride, const int32_t *status,
                    const double *alphas, const SfGeom &g, int nsplit, double *part, hipStream_t st) {
   constexpr int NK1 = SF_LR_K / 4, NK2 = SF_LR_K2 / 4;
-  if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_sweep4r<0, 8, NK1>), sw4r_lds(NK1))) return rc;
-  if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_sweep4r<0, 4, NK1>), sw4r_lds(NK1))) return rc;
-  if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_sweep4r<0, 4, NK2>), sw4r_lds(NK2))) return rc;
   int rows = sf_cdiv(g.lines, nsplit);
   rows = (rows + 127) / 128 * 128;
 #define SW4R_ARGS xt, mask_t, nuse, mu, ufrag, wfrag2, lrok, lam, wfrag, wstride, status, alphas, g.nalpha, g.lines, g.p, g.ps, rows, part
@@ -708,42 +679,31 @@ int launch_sweep4r(const float *xt, const uint8_t *mask_t, const int32_t *nuse, 
     if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_sweep4s<NK1>), SwS<NK1>::lds_bytes())) return rc;
     const int sfast = sf_tune().sweep_grid != 1;
     const dim3 grid = sfast ? dim3(nsplit, g.ncols) : dim3(g.ncols, nsplit);
-    if (form == 0 || form == 3 || form == 5) hipLaunchKernelGGL((k_sweep4s<NK1>), grid, dim3(512), SwS<NK1>::lds_bytes(), st, SW4R_ARGS, sfast);
+    if (form != 4) {
+      hipLaunchKernelGGL((k_sweep4s<NK1>), grid, dim3(512), SwS<NK1>::lds_bytes(), st, SW4R_ARGS, sfast);
+    } else {   // renormalisation after every tile (the form of the round's first half): the bit-identity test
+      if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_sweep4s<NK1, 1>), SwS<NK1>::lds_bytes())) return rc;
+      hipLaunchKernelGGL((k_sweep4s<NK1, 1>), grid, dim3(512), SwS<NK1>::lds_bytes(), st, SW4R_ARGS, sfast);
+    }
     if (form == 0) {   // rank 24 (lrok == 3; the factorisation offers it only to this form: sf_launch_sweep4)
       constexpr int NK0 = SF_LR_K0 / 4;
       if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_sweep4s<NK0>), SwS<NK0>::lds_bytes())) return rc;
       hipLaunchKernelGGL((k_sweep4s<NK0>), grid, dim3(512), SwS<NK0>::lds_bytes(), st, SW4R_ARGS, sfast);
     }
-    if (form == 4) {   // renormalisation after every tile (the form of the round's first half): A/B and the bit-identity test
-      if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_sweep4s<NK1, 0, 1>), SwS<NK1>::lds_bytes())) return rc;
-      hipLaunchKernelGGL((k_sweep4s<NK1, 0, 1>), grid, dim3(512), SwS<NK1>::lds_bytes(), st, SW4R_ARGS, sfast);
-    }
-#ifdef SF_SWEEP_EXPERIMENTS
-#define SW4S_EXP(E) if (form == 100 + E) { \
-      if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_sweep4s<NK1, E>), SwS<NK1>::lds_bytes())) return rc; \
-      hipLaunchKernelGGL((k_sweep4s<NK1, E>), grid, dim3(512), SwS<NK1>::lds_bytes(), st, SW4R_ARGS, sfast); }
-    SW4S_EXP(1) SW4S_EXP(2) SW4S_EXP(4) SW4S_EXP(5) SW4S_EXP(8) SW4S_EXP(16) SW4S_EXP(31) SW4S_EXP(32) SW4S_EXP(64) SW4S_EXP(96)
-#endif
     SF_LAUNCH_CHECK("k_sweep4s");
     // rank 36 (lrok == 2): the streamed kernel fits two waves per SIMD there too (250 registers; round 2's k_sweep4r needed
     // one wave per SIMD for its wider t copies): 2.90 against 3.41 ms per stage-5 call on 256 rank-36 columns
-    // (tools/tune_sweep_rank36.py); sf_debug_set(20, 3) keeps k_sweep4r<0,4,9> for these columns
-    if (form != 3) {
-      if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_sweep4s<NK2>), SwS<NK2>::lds_bytes())) return rc;
-      hipLaunchKernelGGL((k_sweep4s<NK2>), grid, dim3(512), SwS<NK2>::lds_bytes(), st, SW4R_ARGS, sfast);
-    } else {
-      hipLaunchKernelGGL((k_sweep4r<0, 4, NK2>), dim3(g.ncols, nsplit), dim3(256), sw4r_lds(NK2), st, SW4R_ARGS);
-    }
+    if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_sweep4s<NK2>), SwS<NK2>::lds_bytes())) return rc;
+    hipLaunchKernelGGL((k_sweep4s<NK2>), grid, dim3(512), SwS<NK2>::lds_bytes(), st, SW4R_ARGS, sfast);
     SF_LAUNCH_CHECK("k_sweep4s(rank 36)");
     return 0;
   }
-  if (sf_tune().sweep4r_waves == 4)
-    hipLaunchKernelGGL((k_sweep4r<0, 4, NK1>), dim3(g.ncols, nsplit), dim3(256), sw4r_lds(NK1), st, SW4R_ARGS);
-  else
-    hipLaunchKernelGGL((k_sweep4r<0, 8, NK1>), dim3(g.ncols, nsplit), dim3(512), sw4r_lds(NK1), st, SW4R_ARGS);
+  if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_sweep4r<8, NK1>), sw4r_lds(NK1))) return rc;
+  if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_sweep4r<4, NK2>), sw4r_lds(NK2))) return rc;
+  hipLaunchKernelGGL((k_sweep4r<8, NK1>), dim3(g.ncols, nsplit), dim3(512), sw4r_lds(NK1), st, SW4R_ARGS);
   SF_LAUNCH_CHECK("k_sweep4r");
   // rank 36 (lrok == 2): one wave per SIMD (the wider t registers do not fit two)
-  hipLaunchKernelGGL((k_sweep4r<0, 4, NK2>), dim3(g.ncols, nsplit), dim3(256), sw4r_lds(NK2), st, SW4R_ARGS);
+  hipLaunchKernelGGL((k_sweep4r<4, NK2>), dim3(g.ncols, nsplit), dim3(256), sw4r_lds(NK2), st, SW4R_ARGS);
 #undef SW4R_ARGS
   SF_LAUNCH_CHECK("k_sweep4r");
   return 0;
@@ -758,38 +718,29 @@ int sf_launch_wfrag4(const double *evec, const double *d, const SfGeom &g, size_
   return 0;
 }
 
+// (`int`: the retired sweep-variant knob's argument, always 0 -- the declaration sits in cmf_common.h, whose bytes the score
+//  kernel's PMC record is tied to)
 int sf_launch_sweep4(const float *xt, const uint8_t *mask_t, const int32_t *nuse, const double *mu, const double *lam,
                      const double *wfrag, size_t wstride, const int32_t *status, const double *alphas, const SfGeom &g,
-                     int nsplit, double *part, int variant, void *lr_scratch, hipStream_t st, const int32_t **lrok_out) {
-#define SW4_ARGS xt, mask_t, nuse, mu, lam, wfrag, wstride, status, alphas, g, nsplit, part, st
+                     int nsplit, double *part, int, void *lr_scratch, hipStream_t st, const int32_t **lrok_out) {
+  // rank-factored sweep for the columns whose factorisation is accepted, the full-rank kernel for the rest
+  // (it returns at once for the others: a column is swept by exactly one of the two)
+  if (!lr_scratch) { sf_set_error("sf_launch_sweep4: the 4x4x4 sweeps need the rank-factorisation scratch"); return -2; }
   const int nj = sf_sw4_groups(g.p), nje = nj + (nj & 1);
-  if ((variant == 0 && lr_scratch) || nj > S4J) {
-    // rank-factored sweep for the columns whose factorisation is accepted, the full-rank kernel for the rest
-    // (it returns at once for the others: a column is swept by exactly one of the two)
-    if (!lr_scratch) { sf_set_error("sf_launch_sweep4: windows of 21 / 24 band groups need the rank-factorisation scratch"); return -2; }
-    char *base = reinterpret_cast<char *>(lr_scratch);
-    double *ufrag = reinterpret_cast<double *>(base);
-    double *wfrag2 = reinterpret_cast<double *>(base + sf_align((size_t)g.ncols * nje * (SF_LR_K2 / 4) * 16 * sizeof(double)));
-    int32_t *lrok = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(wfrag2) +
-                                                sf_align((size_t)g.ncols * S4M * (SF_LR_K2 / 4) * 64 * sizeof(double)));
-    if (lrok_out) *lrok_out = lrok;
-    // (the rank-24 tier exists in the streamed kernel only: the debug forms of sf_debug_set(20, .) sweep ranks 28 / 36; form 5 is
-    //  the default with that tier switched off -- what the bit-for-bit comparisons against forms 1 and 4 run)
-    if (int rc = sf_launch_lowrank(lam, nuse, status, alphas, g, ufrag, wfrag2, lrok, st, nj > S4J || sf_tune().sweep4_form == 0)) return rc;
-    if (nj == 21)
-      return sf_launch_sweep4s_21(xt, mask_t, nuse, mu, ufrag, wfrag2, lrok, lam, wfrag, wstride, status, alphas, g, nsplit, part, st);
-    if (nj == 24)
-      return sf_launch_sweep4s_24(xt, mask_t, nuse, mu, ufrag, wfrag2, lrok, lam, wfrag, wstride, status, alphas, g, nsplit, part, st);
-    if (int rc = launch_sweep4r(xt, mask_t, nuse, mu, ufrag, wfrag2, lrok, lam, wfrag, wstride, status, alphas, g, nsplit, part, st))
-      return rc;
-    return launch_sweep4_t<0>(SW4_ARGS, lrok);
-  }
-#ifdef SF_SWEEP_EXPERIMENTS
-  if (variant == 11) return launch_sweep4_t<1>(SW4_ARGS);
-  if (variant == 12) return launch_sweep4_t<2>(SW4_ARGS);
-  if (variant == 13) return launch_sweep4_t<3>(SW4_ARGS);
-  if (variant == 14) return launch_sweep4_t<4>(SW4_ARGS);
-#endif
-  return launch_sweep4_t<0>(SW4_ARGS);
-#undef SW4_ARGS
+  char *base = reinterpret_cast<char *>(lr_scratch);
+  double *ufrag = reinterpret_cast<double *>(base);
+  double *wfrag2 = reinterpret_cast<double *>(base + sf_align((size_t)g.ncols * nje * (SF_LR_K2 / 4) * 16 * sizeof(double)));
+  int32_t *lrok = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(wfrag2) +
+                                              sf_align((size_t)g.ncols * S4M * (SF_LR_K2 / 4) * 64 * sizeof(double)));
+  if (lrok_out) *lrok_out = lrok;
+  // (the rank-24 tier exists in the streamed kernel only: the debug forms of sf_debug_set(20, .) sweep ranks 28 / 36; form 5 is
+  //  the default with that tier switched off -- what the bit-for-bit comparisons against forms 1 and 4 run)
+  if (int rc = sf_launch_lowrank(lam, nuse, status, alphas, g, ufrag, wfrag2, lrok, st, nj > S4J || sf_tune().sweep4_form == 0)) return rc;
+  if (nj == 21)
+    return sf_launch_sweep4s_21(xt, mask_t, nuse, mu, ufrag, wfrag2, lrok, lam, wfrag, wstride, status, alphas, g, nsplit, part, st);
+  if (nj == 24)
+    return sf_launch_sweep4s_24(xt, mask_t, nuse, mu, ufrag, wfrag2, lrok, lam, wfrag, wstride, status, alphas, g, nsplit, part, st);
+  if (int rc = launch_sweep4r(xt, mask_t, nuse, mu, ufrag, wfrag2, lrok, lam, wfrag, wstride, status, alphas, g, nsplit, part, st))
+    return rc;
+  return launch_sweep4(xt, mask_t, nuse, mu, lam, wfrag, wstride, status, alphas, g, nsplit, part, st, lrok);
 }

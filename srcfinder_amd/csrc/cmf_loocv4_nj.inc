@@ -16,15 +16,15 @@ int launch_sweep4s_nj(const float *xt, const uint8_t *mask_t, const int32_t *nus
   rows = (rows + 127) / 128 * 128;
   const dim3 grid(nsplit, g.ncols);
   using S1 = SwS<NK1, NJ>;
-  if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_sweep4s<NK1, 0, 4, NJ>), S1::lds_bytes())) return rc;
-  hipLaunchKernelGGL((k_sweep4s<NK1, 0, 4, NJ>), grid, dim3(512), S1::lds_bytes(), st, xt, mask_t, nuse, mu, ufrag, wfrag2, lrok, lam,
+  if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_sweep4s<NK1, 4, NJ>), S1::lds_bytes())) return rc;
+  hipLaunchKernelGGL((k_sweep4s<NK1, 4, NJ>), grid, dim3(512), S1::lds_bytes(), st, xt, mask_t, nuse, mu, ufrag, wfrag2, lrok, lam,
                      wfrag, wstride, status, alphas, g.nalpha, g.lines, g.p, g.ps, rows, part, 1);
   SF_LAUNCH_CHECK("k_sweep4s");
   {
     constexpr int NK0 = SF_LR_K0 / 4;
     using S0 = SwS<NK0, NJ>;
-    if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_sweep4s<NK0, 0, 4, NJ>), S0::lds_bytes())) return rc;
-    hipLaunchKernelGGL((k_sweep4s<NK0, 0, 4, NJ>), grid, dim3(512), S0::lds_bytes(), st, xt, mask_t, nuse, mu, ufrag, wfrag2, lrok, lam,
+    if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_sweep4s<NK0, 4, NJ>), S0::lds_bytes())) return rc;
+    hipLaunchKernelGGL((k_sweep4s<NK0, 4, NJ>), grid, dim3(512), S0::lds_bytes(), st, xt, mask_t, nuse, mu, ufrag, wfrag2, lrok, lam,
                        wfrag, wstride, status, alphas, g.nalpha, g.lines, g.p, g.ps, rows, part, 1);
     SF_LAUNCH_CHECK("k_sweep4s(rank 24)");
   }
@@ -34,8 +34,8 @@ int launch_sweep4s_nj(const float *xt, const uint8_t *mask_t, const int32_t *nus
                 "rank-36 tier: the LDS fit of k_sweep4s<NK2, NJ> must agree with k_lowrank's `NJ == 24 -> refuse` (cmf_lowrank.hip)");
   if constexpr (NJ != 24) {
     using S2 = SwS<NK2, NJ>;
-    if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_sweep4s<NK2, 0, 4, NJ>), S2::lds_bytes())) return rc;
-    hipLaunchKernelGGL((k_sweep4s<NK2, 0, 4, NJ>), grid, dim3(512), S2::lds_bytes(), st, xt, mask_t, nuse, mu, ufrag, wfrag2, lrok,
+    if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_sweep4s<NK2, 4, NJ>), S2::lds_bytes())) return rc;
+    hipLaunchKernelGGL((k_sweep4s<NK2, 4, NJ>), grid, dim3(512), S2::lds_bytes(), st, xt, mask_t, nuse, mu, ufrag, wfrag2, lrok,
                        lam, wfrag, wstride, status, alphas, g.nalpha, g.lines, g.p, g.ps, rows, part, 1);
     SF_LAUNCH_CHECK("k_sweep4s(rank 36)");
   }

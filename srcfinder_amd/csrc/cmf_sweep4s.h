@@ -44,7 +44,7 @@ __device__ __forceinline__ double dpp_row(double v) {
 //   What it does NOT do is get rid of the vector instructions, and they are what is left: on gfx950 every VALU instruction
 //   issued beside the 4x4x4 fp64 MFMA stream costs ~6 cycles of matrix time even with two waves per SIMD
 //   (tools/microbench/mix4w.hip: 3 VALU per 8 MFMA take the pipe from 72 to 56 TFLOP/s -- this kernel's rate; LDS reads,
-//   s_waitcnt and s_nop are free).  Measured by leaving a class out (SF_SWEEP_EXPERIMENTS, results wrong, MFMAs kept):
+//   s_waitcnt and s_nop are free).  Measured by leaving a class out (a timing build, results wrong, MFMAs kept):
 //   the row reduction (221 of the 323) 0.40 ms, conversion + centring (36) 0.19 ms, the 42 DPP moves 0.05 ms, squares
 //   and validity selects 0.03 + 0.05 ms; with every one of them gone the launch is 4.9 ms, not 4.2: profiles/r03_sweep_ablation.txt.
 //   (The hardware's A-block broadcast -- cbsz / abid, which would replace the three DPP-rotated copies of t -- assembles
@@ -117,13 +117,10 @@ __device__ __forceinline__ void lds_await_all(d2_t (&m)[N]) {
   lds_tie<0, N>(m);
 }
 
-// EXP (timing experiments, wrong results, -DSF_SWEEP_EXPERIMENTS): bit 0 no row reduction, 1 no conversion / centring,
-// 2 no DPP rotations, 3 no squares, 4 no validity selects -- the MFMAs and LDS reads stay; bit 5 no tiles at all (what the
-// table prologue + epilogue of every workgroup cost), bit 6 no table prologue (tiles on whatever the LDS holds)
 // RN: the running products are renormalised (mantissa / exponent split) after every RN-th tile of a wave.  A nonzero finite q of this
 // sweep lies in [~1e-17, ~1e3] (1 + a sum of O(1) terms in fp64), so the product of the 4 RN = 16 values a lane folds in between two
 // splits stays inside [1e-272, 1e48]: scaling by powers of two is exact there, the results are bit-identical to RN = 1.
-template <int NK, int EXP = 0, int RN = 4, int NJT = S4J>
+template <int NK, int RN = 4, int NJT = S4J>
 __global__ __launch_bounds__(512, 1) void k_sweep4s(const float *__restrict__ xt, const uint8_t *__restrict__ mask_t,
                                                     const int32_t *__restrict__ nuse, const double *__restrict__ mu,
                                                     const double *__restrict__ ufrag_g, const double *__restrict__ wfrag2_g,
@@ -148,7 +145,7 @@ __global__ __launch_bounds__(512, 1) void k_sweep4s(const float *__restrict__ xt
   // ---- prologue: the tables, permuted into the pair layouts.  Every global load of the workgroup is issued first (16-byte
   // loads, compile-time trip counts: ~17 per thread in flight at once), then the LDS stores: with one workgroup per CU
   // nothing else runs on the CU meanwhile, and a load-store loop paid one L2 round trip per iteration
-  if constexpr ((EXP & 64) == 0) {
+  {
     constexpr int NT = 64 * NW;
     constexpr int NW2 = NJ * NJE * 8, NU2 = NJE * NKP * 16, NF2 = R3 * 64, NL2 = NK * 32;   // 16-byte pieces of the four tables
     constexpr int IW = (NW2 + NT - 1) / NT, IU = (NU2 + NT - 1) / NT, IF = (NF2 + NT - 1) / NT, IL = (NL2 + NT - 1) / NT;
@@ -222,7 +219,7 @@ __global__ __launch_bounds__(512, 1) void k_sweep4s(const float *__restrict__ xt
   int ntile = 0;
   int nrowok = 0;   // valid rows seen by this lane (lanes with g == 0 cover every row of the wave's tiles once)
 
-  const int rbeg = split * rows_per_wg, rend = (EXP & 32) ? rbeg : min(L, rbeg + rows_per_wg);
+  const int rbeg = split * rows_per_wg, rend = min(L, rbeg + rows_per_wg);
   const uint8_t *mp = mask_t + (size_t)c * L;
   const float *xc = xt + (size_t)c * L * PS + NJ * g;
   const unsigned smb = (unsigned)(size_t)sm;
@@ -265,10 +262,6 @@ __global__ __launch_bounds__(512, 1) void k_sweep4s(const float *__restrict__ xt
     auto cvt = [&](auto sc) {     // x[s] = row value - column mean  (fp64, as the reference centres)
       constexpr int s = decltype(sc)::value;
       double v = (double)xraw[s] - ((s & 1) ? mur[s >> 1].y : mur[s >> 1].x);
-      if constexpr ((EXP & 2) != 0) {
-        v = (s & 1) ? mur[s >> 1].y : mur[s >> 1].x;
-        asm volatile("" :: "v"(xraw[s]));
-      }
       if constexpr (3 * NJ + s >= 4 * NJ - 3) v = (NJ * g + s < p) ? v : 0.0;   // p >= 69: only bands 69..71 can lie beyond the window
       x[s] = v;
     };
@@ -308,13 +301,6 @@ __global__ __launch_bounds__(512, 1) void k_sweep4s(const float *__restrict__ xt
       }
     };
     auto reduce_group = [&](auto grc) {
-      if constexpr ((EXP & 1) != 0) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) asm volatile("" :: "v"(acc[k][q]));
-        return;
-      }
       static_for<0, (RN == 1 ? 4 : 3)>([&](auto sc) { reduce_stage(grc, sc); });
     };
 
@@ -341,7 +327,7 @@ __global__ __launch_bounds__(512, 1) void k_sweep4s(const float *__restrict__ xt
         if constexpr (u == (NJ - 2) * (NJE / 2)) {   // every raw value is converted: the next tile's rows may land in xraw
           if (r0 + 16 * NW < rend) fetch(r0 + 16 * NW, xraw, rowok_next);
         }
-        if constexpr (u == R1 - 1 && (EXP & 8) == 0) z[0] = z[0] * z[0];
+        if constexpr (u == R1 - 1) z[0] = z[0] * z[0];
       } else if constexpr (u < R1 + R2) {
         constexpr int v = u - R1, jg = v / NKP, mg = 2 * (v % NKP);
         if constexpr (jg == 0) {
@@ -351,21 +337,15 @@ __global__ __launch_bounds__(512, 1) void k_sweep4s(const float *__restrict__ xt
           t[0][mg] = __builtin_amdgcn_mfma_f64_4x4x4f64(ring[slot].x, z[jg], t[0][mg], 0, 0, 0);
           if constexpr (mg + 1 < NK) t[0][mg + 1] = __builtin_amdgcn_mfma_f64_4x4x4f64(ring[slot].y, z[jg], t[0][mg + 1], 0, 0, 0);
         }
-        if constexpr (mg == 2 && jg + 1 < NJE && (EXP & 8) == 0) z[jg + 1] = z[jg + 1] * z[jg + 1];   // the square the next eigen group multiplies
+        if constexpr (mg == 2 && jg + 1 < NJE) z[jg + 1] = z[jg + 1] * z[jg + 1];   // the square the next eigen group multiplies
         if constexpr (u == R1 + R2 - 1) {   // an invalid row leaves every q of the tile at 1
-          if constexpr ((EXP & 16) == 0) {
 #pragma unroll
-            for (int m = 0; m < NK; ++m) t[0][m] = rowok ? t[0][m] : 0.0;
-          }
+          for (int m = 0; m < NK; ++m) t[0][m] = rowok ? t[0][m] : 0.0;
 #pragma unroll
           for (int m = 0; m < NK; ++m) {   // block m of rotation s meets row group (m + s) % 4
-            if constexpr ((EXP & 4) != 0) {
-              t[1][m] = t[2][m] = t[3][m] = t[0][m];
-            } else {
-              t[1][m] = dpp_row<0x124>(t[0][m]);  // row_ror:4
-              t[2][m] = dpp_row<0x128>(t[0][m]);  // row_ror:8
-              t[3][m] = dpp_row<0x12C>(t[0][m]);  // row_ror:12
-            }
+            t[1][m] = dpp_row<0x124>(t[0][m]);  // row_ror:4
+            t[2][m] = dpp_row<0x128>(t[0][m]);  // row_ror:8
+            t[3][m] = dpp_row<0x12C>(t[0][m]);  // row_ror:12
           }
         }
       } else if constexpr (u < R1 + R2 + R3) {
@@ -375,9 +355,7 @@ __global__ __launch_bounds__(512, 1) void k_sweep4s(const float *__restrict__ xt
           const double b = kk ? ring[slot].y : ring[slot].x;
           static_for<0, 4>([&](auto sc) {
             constexpr int s = decltype(sc)::value;
-            if constexpr (jg == 0 && (EXP & 4) != 0)   // distinct chains although the four A operands are the same register
-              acc[k][s] = __builtin_amdgcn_mfma_f64_4x4x4f64(t[s][jg], b, s == 0 ? 1.0 : (s == 1 ? 2.0 : (s == 2 ? 0.5 : 4.0)), 0, 0, 0);
-            else if constexpr (jg == 0) acc[k][s] = __builtin_amdgcn_mfma_f64_4x4x4f64(t[s][jg], b, 1.0, 0, 0, 0);
+            if constexpr (jg == 0) acc[k][s] = __builtin_amdgcn_mfma_f64_4x4x4f64(t[s][jg], b, 1.0, 0, 0, 0);
             else acc[k][s] = __builtin_amdgcn_mfma_f64_4x4x4f64(t[s][jg], b, acc[k][s], 0, 0, 0);
           });
         });
@@ -386,9 +364,7 @@ __global__ __launch_bounds__(512, 1) void k_sweep4s(const float *__restrict__ xt
         constexpr int jg = u - R1 - R2 - R3;
         static_for<0, 4>([&](auto sc) {
           constexpr int s = decltype(sc)::value;
-          if constexpr (jg == 0 && (EXP & 4) != 0)
-            acc[0][s] = __builtin_amdgcn_mfma_f64_4x4x4f64(t[s][jg], ringl[slot], s == 0 ? 1.0 : (s == 1 ? 2.0 : (s == 2 ? 0.5 : 4.0)), 0, 0, 0);
-          else if constexpr (jg == 0) acc[0][s] = __builtin_amdgcn_mfma_f64_4x4x4f64(t[s][jg], ringl[slot], 1.0, 0, 0, 0);
+          if constexpr (jg == 0) acc[0][s] = __builtin_amdgcn_mfma_f64_4x4x4f64(t[s][jg], ringl[slot], 1.0, 0, 0, 0);
           else acc[0][s] = __builtin_amdgcn_mfma_f64_4x4x4f64(t[s][jg], ringl[slot], acc[0][s], 0, 0, 0);
         });
         if constexpr (jg == NK - 1) {

@@ -414,8 +414,8 @@ int run_batch(Net &N, const float *padded, const float *plane, int H, int W, lon
     if ((rc = peak(x, (size_t)n * hw * hw * cin, 2 + 3 * i))) return rc;
     // branch1 | 3x3 reduce | "5x5" reduce in one GEMM, then the two 3x3 convolutions, the pool branch (:184-228)
     // inception4e on the split route: maxpool4 (2 x 2 / 2 on 16 x 16, :75) is taken in the four producers' epilogues (round 6: the pool
-    // kernel read 436 MB to write 109) -- the block's output lands as [n][8][8][cout]; sf_debug_set(16, 4) keeps the pool kernel
-    const bool pool4 = use_split && i == 6 && hw == 16 && sf_cnn_pool_conv_split_ok(n, hw, hw, cin, s.pp) && sf_tune().cnn_variant != 4;
+    // kernel read 436 MB to write 109) -- the block's output lands as [n][8][8][cout]
+    const bool pool4 = use_split && i == 6 && hw == 16 && sf_cnn_pool_conv_split_ok(n, hw, hw, cin, s.pp);
     if (pool4)
       rc = sfi_cnn_conv_split3_pool2(x, n, cin, cin, N.shalf + N.SL.head3[i].h, half_lo(N, N.SL.head3[i], s.c1 + s.c3r + s.c5r, 1, cin),
                                      N.sscale + N.SL.head3[i].s, B_(N.L.head3[i]), s.c1, s.c3r, s.c5r, ax, y, cout, 0, N.t2, N.t3, a2, a3, flag, stream);

@@ -637,7 +637,7 @@ static int split_go(const float *in, int in_split, int N, int H, int W, int Cin,
     auto cd = [](long long a, long long b) { return (a + b - 1) / b; };
     const long long load_now = cd(cd(Ml, bm) * cd(Cout, bn), 256) * bm * bn;
     const long long load_160 = cd(cd(Ml, 128) * cd(Cout, 160), 256) * 128 * 160;
-    if (Cout > 128 && load_160 * 20 < load_now * 19 && sf_tune().cnn_variant != 2)
+    if (Cout > 128 && load_160 * 20 < load_now * 19)
       return launch_split<160>(in, in_split, (int)Ml, H, W, Cin, ld_in, h, l, wscale, bias, Cout, ksize, ascale, d, overflow, st, rows);
   }
   if (Cout > 64 && sf_cdiv(Cout, 128) * 128 <= sf_cdiv(Cout, 64) * 64)

@@ -23,8 +23,8 @@
 // applies A^T . A to its (block, channel) items, adds the folded-BatchNorm bias, ReLU, and stores 32 consecutive channels.
 // Measured (profiles/r05_cnn_layers.txt, tools/check_conv.py --time): 1.3-1.6 x the direct kernel on the layers with >= 64
 // input channels, i.e. 0.47-0.55 of the matrix peak on the Winograd flop count -- the instruction stream AROUND the MFMAs
-// (staging 0.34 ms, transform 0.62 ms, stores 0.39 ms, fragment reads and barriers 1.4 ms of conv3's 2.7 ms, timed with the
-// EXP arms below) is the bound, not the matrix pipe (1.31 ms).
+// (staging 0.34 ms, transform 0.62 ms, stores 0.39 ms, fragment reads and barriers 1.4 ms of conv3's 2.7 ms, timed with
+// those parts left out) is the bound, not the matrix pipe (1.31 ms).
 #include "cmf_common.h"
 #include <type_traits>
 
@@ -63,9 +63,7 @@ __device__ __forceinline__ float4 wn_sub(float4 a, float4 b) { return make_float
 //   iteration c:  barrier | stage U(c + 1) and the raw pixels of chunk c + 2 from registers, request chunk c + 3's pixels and
 //                 U(c + 2) | transform chunk c + 1 (raw -> V) BETWEEN the MFMAs of chunk c (the matrix instructions are
 //                 asynchronous: the transform's 8 reads, 32 additions and 4 writes per thread ride in their shadow).
-// EXP (timing experiments, wrong results, -DSF_CONV_EXPERIMENTS + sf_debug_set(17, 10 + bits)): 1 no staging / loads after the
-// prologue, 2 no input transform, 4 no MFMAs, 8 no epilogue stores
-template <int BN, int EXP = 0>
+template <int BN>
 __global__ __launch_bounds__(WN_NT) void k_wino(const float *__restrict__ in, int N, int H, int W, int Cin, int ld_in,
                                                  const float *__restrict__ U, const float *__restrict__ bias, int Cout,
                                                  float *__restrict__ out, int ld_out, int ch_off, int TYX) {
@@ -212,13 +210,11 @@ __global__ __launch_bounds__(WN_NT) void k_wino(const float *__restrict__ in, in
     __syncthreads();   // V(c), U(c) and the raw pixels of chunk c + 1 are complete; everybody is past chunk c - 1
     // stage what the registers hold: U(c + 1) (its buffer was read by the MFMAs of chunk c - 1), the pixels of chunk c + 2 (their
     // buffer was read by the transform of chunk c in the last iteration); then request the next ones
-    if (!(EXP & 1)) {
-      stage_u(nxt);
-      stage_raw(cur);
-      gload_raw(c + 3);
-      gload_u(c + 2);
-    }
-    const bool more = (EXP & 2) ? false : c + 1 < nc;
+    stage_u(nxt);
+    stage_raw(cur);
+    gload_raw(c + 3);
+    gload_u(c + 2);
+    const bool more = c + 1 < nc;
     const float *V = wn_lds + cur * BUFF + RAWF, *Ub = V + VF;
     float4 a4[2][2], b4[2][NTN];
 #pragma unroll
@@ -234,21 +230,14 @@ __global__ __launch_bounds__(WN_NT) void k_wino(const float *__restrict__ in, in
     for (int xl = 0; xl < 2; ++xl) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        if (!(EXP & 4)) {
 #pragma unroll
-          for (int mb = 0; mb < 2; ++mb)
+        for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
-            for (int nt = 0; nt < NTN; ++nt) {
-              const float av = j == 0 ? a4[xl][mb].x : (j == 1 ? a4[xl][mb].y : (j == 2 ? a4[xl][mb].z : a4[xl][mb].w));
-              const float bv = j == 0 ? b4[xl][nt].x : (j == 1 ? b4[xl][nt].y : (j == 2 ? b4[xl][nt].z : b4[xl][nt].w));
-              acc[xl][mb][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[xl][mb][nt], 0, 0, 0);
-            }
-        } else if (j == 0) {
-#pragma unroll
-          for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-            for (int nt = 0; nt < NTN; ++nt) acc[xl][mb][nt][0] += a4[xl][mb].x * b4[xl][nt].x + a4[xl][mb].w * b4[xl][nt].w;
-        }
+          for (int nt = 0; nt < NTN; ++nt) {
+            const float av = j == 0 ? a4[xl][mb].x : (j == 1 ? a4[xl][mb].y : (j == 2 ? a4[xl][mb].z : a4[xl][mb].w));
+            const float bv = j == 0 ? b4[xl][nt].x : (j == 1 ? b4[xl][nt].y : (j == 2 ? b4[xl][nt].z : b4[xl][nt].w));
+            acc[xl][mb][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[xl][mb][nt], 0, 0, 0);
+          }
         if (xl == 0 && j == 1) {                 // the transform of the next chunk rides between the MFMA groups
           __builtin_amdgcn_sched_barrier(0);
           if (more) tf_math();
@@ -300,10 +289,8 @@ __global__ __launch_bounds__(WN_NT) void k_wino(const float *__restrict__ in, in
           const float y0 = (tm[i][0] + tm[i][1]) + tm[i][2], y1 = (tm[i][1] - tm[i][2]) - tm[i][3];
           const int oy = oy0 + 2 * ty + i, ox = ox0 + 2 * tx;
           float *op = out + (((size_t)n * H + oy) * W + ox) * ld_out + ch_off + co;
-          if (!(EXP & 8) || y0 == 1.2345f) {
-            op[0] = fmaxf(y0 + bb, 0.f);
-            op[ld_out] = fmaxf(y1 + bb, 0.f);
-          }
+          op[0] = fmaxf(y0 + bb, 0.f);
+          op[ld_out] = fmaxf(y1 + bb, 0.f);
         }
       }
     }
@@ -356,18 +343,6 @@ int sf_cnn_conv3x3_wino(const float *in, int N, int H, int W, int Cin, int ld_in
   const int TYX = (W >= 16) ? 8 : 4, NI = 64 / (TYX * TYX);
   const int groups = (NI == 1) ? N * (H / 16) * (W / 16) : sf_cdiv(N, NI);
   hipStream_t st = (hipStream_t)stream;
-#ifdef SF_CONV_EXPERIMENTS
-#define WN_EXP(E)                                                                                                                \
-  if (sf_tune().cnn_conv_variant == 10 + E) {                                                                                    \
-    const size_t lds = wino_lds<64>();                                                                                           \
-    if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_wino<64, E>), lds)) return rc;                                     \
-    hipLaunchKernelGGL((k_wino<64, E>), dim3(groups, sf_cdiv(Cout, 64)), dim3(WN_NT), lds, st, in, N, H, W, Cin, ld_in, U, bias, \
-                       Cout, out, ld_out, ch_off, TYX);                                                                          \
-    SF_LAUNCH_CHECK("k_wino");                                                                                                   \
-    return 0;                                                                                                                    \
-  }
-  WN_EXP(1) WN_EXP(2) WN_EXP(3) WN_EXP(4) WN_EXP(7) WN_EXP(8) WN_EXP(15)
-#endif
   if (Cout > 32) {
     const size_t lds = wino_lds<64>();
     if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_wino<64>), lds)) return rc;

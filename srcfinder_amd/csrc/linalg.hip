@@ -549,7 +549,7 @@ constexpr int DET_GROUP_WIDE = 2;   // wide windows (an LU of 425 x 425 is 3 ms 
 // window entries such a column overflowed the list and which jobs survived depended on the order of the atomics).  An int
 // and a double per entry: 2.4 KB per column.  The p x p work matrices are what costs memory; the job loop strides over them.
 static size_t det_maxjobs(const SfGeom &g) { return (size_t)g.ncols * g.nalpha; }
-static size_t det_slots(const SfGeom &g, size_t maxjobs) {
+static size_t det_nslots(const SfGeom &g, size_t maxjobs) {
   size_t slots = DET_SLOT_BYTES / ((size_t)g.p * g.p * sizeof(double));
   slots = slots < 64 ? 64 : (slots > DET_SLOTS ? DET_SLOTS : slots);
   return maxjobs < slots ? maxjobs : slots;
@@ -557,7 +557,7 @@ static size_t det_slots(const SfGeom &g, size_t maxjobs) {
 size_t sf_exact_det_scratch_bytes(const SfGeom &g, int window) {
   (void)window;
   const size_t maxjobs = det_maxjobs(g);
-  const size_t slots = det_slots(g, maxjobs);
+  const size_t slots = det_nslots(g, maxjobs);
   return sf_align(slots * g.p * g.p * sizeof(double)) + sf_align(maxjobs * sizeof(int32_t)) + sf_align(maxjobs * sizeof(double)) +
          sf_align(sizeof(int32_t)) + sf_align((size_t)g.ncols * 4 * sizeof(int32_t));
 }
@@ -566,10 +566,9 @@ int sf_launch_exact_det(const double *cov, const int32_t *nloo, const int32_t *s
                         int window, const double *rest, double *nll, int32_t *alphaidx, void *scratch, hipStream_t st,
                         const double *target) {
   const size_t maxjobs = det_maxjobs(g);
-  const size_t slots_alloc = det_slots(g, maxjobs);
-  const size_t slots = sf_tune().det_slots > 0 ? std::min(slots_alloc, (size_t)sf_tune().det_slots) : slots_alloc;
+  const size_t slots = det_nslots(g, maxjobs);
   char *p = reinterpret_cast<char *>(scratch);
-  double *work = reinterpret_cast<double *>(p); p += sf_align(slots_alloc * g.p * g.p * sizeof(double));
+  double *work = reinterpret_cast<double *>(p); p += sf_align(slots * g.p * g.p * sizeof(double));
   int32_t *jobs = reinterpret_cast<int32_t *>(p); p += sf_align(maxjobs * sizeof(int32_t));
   double *det = reinterpret_cast<double *>(p); p += sf_align(maxjobs * sizeof(double));
   int32_t *njobs = reinterpret_cast<int32_t *>(p); p += sf_align(sizeof(int32_t));

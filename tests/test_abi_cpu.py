@@ -111,3 +111,52 @@ def test_product_fails_loudly_without_library_or_gpu(monkeypatch, tmp_path):
         if fn.endswith(".py"):
             src = open(os.path.join(pkg, fn)).read()
             assert "import oracle" not in src and "from oracle" not in src, fn
+
+
+def test_tuning_knobs_refuse_retired_forms_and_stay_per_thread():
+    """sf_debug_set refuses a retired key and a retired value of a kept key (an A/B run would otherwise measure the default
+    twice), takes every value the suite, smoke() and bench.py set, and changes only the calling thread's knobs."""
+    import threading
+    L = _ffi.lib()
+    got = ctypes.c_int(0)
+    for key in (4, 5, 8, 19, 26):                                   # retired keys: unknown, as any other unknown key
+        assert L.sf_debug_set(key, 0) == -1 and L.sf_debug_set(key, 1) == -1, key
+        assert b"unknown key" in L.sf_last_error_string()
+        assert L.sf_debug_get(key, ctypes.byref(got)) == -1, key
+    retired = {6: (2, 3, 5, 7, 9), 7: (4, 8, 16), 15: (2,), 16: (2, 4), 17: (10, 11, 12, 14, 25), 20: (2, 3, 100, 101, 196),
+               2: (-1,)}
+    for key, values in retired.items():
+        for v in values:
+            assert L.sf_debug_set(key, v) == -1, (key, v)
+            msg = L.sf_last_error_string()
+            assert b"key %d" % key in msg and b"%d" % v in msg, msg
+            assert L.sf_debug_get(key, ctypes.byref(got)) == 0 and got.value == 0, (key, v)   # the refusal changed nothing
+    used = {1: (0, 5, 7, 100, 200), 2: (0, 4, 64), 3: (0, 1), 6: (0, 1), 7: (0, 2), 10: (0, 1, 6, 7, 8), 14: (0, 1), 15: (0, 1),
+            16: (0, 1, 3), 17: (0, 1, 2, 4), 18: (0, 1, 2, 3), 20: (0, 1, 4, 5), 21: (0, 1), 22: (0, 1), 24: (0, 1, 2, 4, 5)}
+    for key, values in used.items():
+        before = ctypes.c_int(0)
+        assert L.sf_debug_get(key, ctypes.byref(before)) == 0, key
+        for v in values:
+            assert L.sf_debug_set(key, v) == 0, (key, v, L.sf_last_error_string())
+            assert L.sf_debug_get(key, ctypes.byref(got)) == 0 and got.value == v, (key, v)
+        assert L.sf_debug_set(key, before.value) == 0
+    # per calling thread: a knob set here is not seen by another thread, and one set there does not reach this one
+    seen = {}
+
+    def other():
+        v = ctypes.c_int(-1)
+        L.sf_debug_get(20, ctypes.byref(v))
+        seen["before"] = v.value
+        L.sf_debug_set(20, 4)
+        L.sf_debug_get(20, ctypes.byref(v))
+        seen["after"] = v.value
+
+    assert L.sf_debug_set(20, 1) == 0
+    try:
+        t = threading.Thread(target=other)
+        t.start()
+        t.join()
+        assert L.sf_debug_get(20, ctypes.byref(got)) == 0 and got.value == 1
+    finally:
+        L.sf_debug_set(20, 0)
+    assert seen == {"before": 0, "after": 4}

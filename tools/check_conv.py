@@ -103,25 +103,6 @@ def main():
               % (N, H, W, Cin, Cout, ldo, off, err, errd, untouched))
         assert err < 5e-6 and untouched
     print("winograd ok")
-    if "--exp" in sys.argv:
-        import time
-        N, H, Cin, Cout = 512, 64, 64, 192
-        x = torch.relu(torch.randn((N, H, H, Cin), device="cuda"))
-        w = torch.randn((Cout, 9, Cin), device="cuda") / np.sqrt(9 * Cin)
-        b = torch.randn((Cout,), device="cuda")
-        U = torch.empty(L.sf_cnn_wino_weight_floats(Cout, Cin), dtype=torch.float32, device="cuda")
-        L.sf_cnn_wino_weights(_ffi.ptr(w), Cout, Cin, _ffi.ptr(U), _ffi.stream_ptr())
-        out = torch.empty((N, H, H, Cout), device="cuda")
-        for e in (0, 1, 2, 3, 4, 7, 8, 15):
-            L.sf_debug_set(17, 10 + e if e else 0)
-            def run():
-                L.sf_cnn_conv3x3_wino(_ffi.ptr(x), N, H, H, Cin, Cin, _ffi.ptr(U), _ffi.ptr(b), Cout, _ffi.ptr(out), Cout, 0, _ffi.stream_ptr())
-            run(); torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(5): run()
-            torch.cuda.synchronize()
-            print("EXP %2d (1 no staging/loads, 2 no transform, 4 no MFMA, 8 no stores): %.1f us" % (e, (time.perf_counter() - t0) / 5 * 1e6))
-        L.sf_debug_set(17, 0)
     if "--time" in sys.argv:
         import time
         for (N, H, Cin, Cout) in [(512, 64, 64, 192), (512, 32, 96, 128), (512, 32, 128, 192), (512, 16, 160, 320), (512, 16, 96, 208), (512, 8, 192, 384),

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Whole flightlines in flight on DEPTH HIP streams (inter-flightline pipelining): ms per flightline, sequential and pipelined.
-usage: pipeline_probe.py [samples] [depth] [key=value ...]   (sf_debug_set knobs for this thread, e.g. 20=1 8=4)"""
+usage: pipeline_probe.py [samples] [depth] [key=value ...]   (sf_debug_set knobs for this thread, e.g. 20=1)"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
