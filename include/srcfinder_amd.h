@@ -458,7 +458,8 @@ int sf_cnn_head(const float *in, int ntiles, int HW, int C, const float *fcw, co
  * sf_cnn_calibrate: the scales alone (host array of sf_cnn_num_scales() floats: [0] maxpool1's output, [1] conv2's output,
  * [2 + 3 i ...] inception block i's input, its 3 x 3 reducer's output, its "5 x 5" reducer's output); synchronises `stream`. */
 size_t sf_cnn_blob_floats(void);
-size_t sf_cnn_score_workspace_bytes(int batch, int H, int W);   /* H = W = 0: without the trunk-sharing buffers (routes 3, 4, 2, 1; sf_cnn_calibrate) */
+size_t sf_cnn_score_workspace_bytes(int batch, int H, int W);   /* H = W = 0: without the trunk-sharing buffers (routes 3, 4, 2, 1; sf_cnn_calibrate);
+                                                                  else enough for either sharing route (0, 5) on an H x W plane */
 int sf_cnn_num_scales(void);
 int sf_cnn_calibrate(const float *padded, int H, int W, const float *blob, int batch, void *workspace, size_t workspace_bytes,
                      float *scales, void *stream);

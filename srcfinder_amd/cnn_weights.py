@@ -85,3 +85,21 @@ def synthetic_plane(h: int, w: int, seed: int = 7) -> np.ndarray:
     plane[0, :3] = -9999.0
     plane[h // 2, w // 3] = -9999.0
     return plane
+
+
+def synthetic_filled_plane(h: int, w: int, seed: int = 5) -> np.ndarray:
+    """A CMF-like float32 plane with data everywhere: a smooth field over the whole 0..4000 clamp (bilinear between hashed values
+    on a 24-pixel grid), pixel noise, values below 0 and above 4000, ~0.2 % NODATA pixels.  Only + - * / of float64 on
+    ``_uniform`` values: the same bytes on every machine."""
+    cell = 24
+    gh, gw = h // cell + 2, w // cell + 2
+    g = _uniform(10_002, gh * gw, seed).reshape(gh, gw)
+    yy, xx = np.arange(h, dtype=np.float64) / cell, np.arange(w, dtype=np.float64) / cell
+    iy, ix = yy.astype(np.int64), xx.astype(np.int64)
+    fy, fx = (yy - iy)[:, None], (xx - ix)[None, :]
+    field = ((g[iy][:, ix] * (1.0 - fx) + g[iy][:, ix + 1] * fx) * (1.0 - fy)
+             + (g[iy + 1][:, ix] * (1.0 - fx) + g[iy + 1][:, ix + 1] * fx) * fy)
+    noise = _uniform(10_003, h * w, seed).reshape(h, w)
+    plane = (-500.0 + 5000.0 * field + 800.0 * (noise - 0.5)).astype(np.float32)
+    plane[_uniform(10_004, h * w, seed).reshape(h, w) < 0.002] = -9999.0
+    return plane

@@ -217,7 +217,8 @@ struct Net {
   hipStream_t st;
 };
 
-Net make_net(const float *blob, int batch, void *workspace, void *stream, int H = 0, int W = 0, int depth = 0, int r0 = 0, int r1 = 0) {
+Net make_net(const float *blob, int batch, void *workspace, void *stream, int H = 0, int W = 0, int depth = 0, int r0 = 0, int r1 = 0,
+             size_t workspace_bytes = 0) {
   Net N{};
   N.blob = blob;
   N.SH = share_layout(batch, H, W, depth, r1 - r0);
@@ -231,7 +232,9 @@ Net make_net(const float *blob, int batch, void *workspace, void *stream, int H 
   N.shalf = reinterpret_cast<_Float16 *>(N.sscale + N.SL.scales);
   N.flags = reinterpret_cast<int *>(N.shalf + N.SL.halves);
   N.amax = reinterpret_cast<float *>(N.flags + NFLAG);
-  if (N.SH.rows > 0) N.share = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + base_bytes(batch));
+  // (no sharing unless the sharing buffers fit in the caller's workspace)
+  if (N.SH.rows > 0 && base_bytes(batch) + N.SH.total * sizeof(float) <= workspace_bytes)
+    N.share = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + base_bytes(batch));
   N.st = (hipStream_t)stream;
   return N;
 }
@@ -652,7 +655,9 @@ size_t sf_cnn_blob_floats(void) { return blob_layout().total; }
 int sf_cnn_num_scales(void) { return NSCALE; }
 size_t sf_cnn_score_workspace_bytes(int batch, int H, int W) {
   if (batch < 1) return 0;
-  return base_bytes(batch) + sf_align(share_layout(batch, H, W, 2).total * sizeof(float));    // (the deeper form's: it is the larger)
+  // either sharing route's: depth 2 is usually the larger, but where no depth-2 strip fits under the pair limit (total 0) depth 1 still may
+  const size_t d1 = share_layout(batch, H, W, 1).total, d2 = share_layout(batch, H, W, 2).total;
+  return base_bytes(batch) + sf_align((d1 > d2 ? d1 : d2) * sizeof(float));
 }
 
 int sf_cnn_calibrate(const float *padded, int H, int W, const float *blob, int batch, void *workspace, size_t workspace_bytes,
@@ -674,13 +679,15 @@ int sf_cnn_score_rows(const float *padded, const float *plane, int H, int W, int
     return -1;
   }
   const bool sharing = route == 0 || route == 5;       // 0: through inception3b (depth 2); 5: through conv3 (depth 1, round 6's first form)
-  const size_t need = sf_cnn_score_workspace_bytes(batch, sharing ? H : 0, sharing ? W : 0);
+  const int depth = route == 0 ? 2 : 1;
+  // the layout this call builds (its depth), not sf_cnn_score_workspace_bytes' maximum: a caller that sized the workspace by it passes
+  const size_t need = base_bytes(batch) + (sharing ? sf_align(share_layout(batch, H, W, depth).total * sizeof(float)) : 0);
   if (workspace_bytes < need) {
     sf_set_error("sf_cnn_score_rows: workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
     return -4;
   }
   if (info) info[0] = info[1] = 0;          // [0] batches scored again on the fp32 matrix cores, [1] batches that ran on the shared trunk
-  Net N = make_net(blob, batch, workspace, stream, sharing ? H : 0, sharing ? W : 0, route == 0 ? 2 : 1, r0, r1);
+  Net N = make_net(blob, batch, workspace, stream, sharing ? H : 0, sharing ? W : 0, depth, r0, r1, workspace_bytes);
   const long long i0 = (long long)r0 * W, i1 = (long long)r1 * W;
   if (i0 >= i1) return 0;
   int rc = 0;

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Generate the CNN golden vectors with the REAL reference classes (development container only).
 
-    python tests/golden/gen_golden_cnn.py
+    python tests/golden/gen_golden_cnn.py            # cnn_googlenet_golden.npz
+    python tests/golden/gen_golden_cnn.py --filled   # cnn_googlenet_filled_golden.npz: windows full of data
 
 ``cnn/archs/googlenet1.py`` imports as is (torch only).  ``cnn/cnn_pred_pipeline.py`` needs ``torchvision.transforms``
 and ``rasterio`` (absent here): three trivial stand-in classes (Compose / Normalize / Pad) and a ``rasterio.open``
@@ -57,7 +58,12 @@ def install_stubs():
     return Compose, Normalize
 
 
-def main():
+BLOCKS = ["conv1", "maxpool1", "conv2", "conv3", "maxpool2", "inception3a", "inception3b", "maxpool3",
+          "inception4a", "inception4b", "inception4c", "inception4d", "inception4e", "maxpool4", "inception5a", "inception5b"]
+
+
+def reference_model():
+    """(cnn_pred_pipeline module, googlenet1 model with the seed-2024 weights, the COVID_QC transform)."""
     torch.set_num_threads(8)
     Compose, Normalize = install_stubs()
     sys.path.insert(0, os.path.join(REF, "cnn"))
@@ -76,6 +82,11 @@ def main():
 
     mean, std = 110.6390, 183.9152          # COVID_QC, cnn_pred_pipeline.py:126-133
     tf = Compose([P.ClampCH4(vmin=0, vmax=4000), Normalize([mean], [std])])
+    return P, model, tf
+
+
+def main():
+    P, model, tf = reference_model()
 
     # (1) FlightlineConvolve on a 40 x 30 plane with NODATA: padded image + three tiles
     plane = synthetic_plane(40, 30, seed=7)
@@ -91,9 +102,7 @@ def main():
     batch = torch.stack([ds[i] for i in idx6])
     acts = {}
     hooks = []
-    for name in ["conv1", "maxpool1", "conv2", "conv3", "maxpool2", "inception3a", "inception3b", "maxpool3",
-                 "inception4a", "inception4b", "inception4c", "inception4d", "inception4e", "maxpool4",
-                 "inception5a", "inception5b"]:
+    for name in BLOCKS:
         hooks.append(getattr(model, name).register_forward_hook(lambda m, i, o, n=name: acts.__setitem__(n, o.detach())))
     with torch.no_grad():
         logits = model(batch)
@@ -127,5 +136,91 @@ def main():
     print("saliency range", allpred[allpred > -9999].min(), allpred.max())
 
 
+# Windows full of data (the flightline case: > 98 % of a 598-column flightline's windows touch no plane edge).  Two planes,
+# regenerated from (generator, shape, seed) at test time and pinned by a SHA-256 of their bytes:
+#   A  synthetic_plane, 1400 x 300, with NODATA pixels inside the interior block.  Scored in one call at batch 512, the phase maps
+#      are rebuilt every ~506 rows (SHARE_ROWS2 = 512) and, with the default two lanes, the second lane (rows 700..) rebuilds its
+#      maps at row 1206: rows 1232..1239 are served by rebuilt maps, and they straddle a strip-map rebuild (STRIP_ROWS = 16) at
+#      row 1235 with one lane and at 1237 with two.
+#   B  synthetic_filled_plane, 320 x 300: data everywhere over the whole 0..4000 clamp, values outside it, NODATA pixels.
+# Pinned per plane: an 8 x 8 block of consecutive interior windows (every phase of the 64-grid and 32-grid maps, >= 128 px from
+# every edge), four windows that each hang over exactly one plane edge, the four corners, one interior NODATA pixel.
+FILLED = {
+    "A": dict(gen="synthetic_plane", H=1400, W=300, seed=41, block=(1232, 140), nodata=[(1234, 143), (1238, 146)]),
+    "B": dict(gen="synthetic_filled_plane", H=320, W=300, seed=5, block=(148, 140), nodata=[]),
+}
+
+
+def filled_plane(key):
+    from srcfinder_amd import cnn_weights
+    c = FILLED[key]
+    plane = getattr(cnn_weights, c["gen"])(c["H"], c["W"], seed=c["seed"])
+    for r, q in c["nodata"]:
+        plane[r, q] = -9999.0
+    return plane
+
+
+def filled_windows(key, plane):
+    """(flat window indices, kind per window) of the pinned windows of plane `key`."""
+    c = FILLED[key]
+    H, W = plane.shape
+    br, bc = c["block"]
+    assert 128 <= br and br + 7 <= H - 129 and 128 <= bc and bc + 7 <= W - 129
+    rc = [((br + i, bc + j), "block") for i in range(8) for j in range(8)]
+    rc += [((3, W // 2), "edge_top"), ((H - 4, W // 2 + 5), "edge_bottom"), ((br + 3, 2), "edge_left"), ((br + 4, W - 3), "edge_right")]
+    rc += [((0, 0), "corner"), ((0, W - 1), "corner"), ((H - 1, 0), "corner"), ((H - 1, W - 1), "corner")]
+    blk = np.zeros(plane.shape, bool)
+    blk[br:br + 8, bc:bc + 8] = True
+    inner = np.zeros(plane.shape, bool)
+    inner[128:H - 128, 128:W - 128] = True
+    nod = np.argwhere((plane == -9999) & inner)
+    assert len(nod), key
+    if not any(blk[tuple(x)] for x in nod):                         # (else the block already holds one)
+        rc.append((tuple(int(v) for v in nod[0]), "nodata"))
+    idx = np.array([r * W + q for (r, q), _ in rc], np.int64)
+    assert len(set(idx.tolist())) == len(idx)
+    return idx, np.array([k for _, k in rc])
+
+
+def main_filled():
+    import hashlib
+    P, model, tf = reference_model()
+    out = {}
+    for key in ("A", "B"):
+        plane = filled_plane(key)
+        name = "filled_" + key
+        PLANE[name] = plane
+        ds = P.FlightlineConvolve(name, transform=tf)
+        idx, kind = filled_windows(key, plane)
+        sums, count, logits = {}, 0, []
+        hooks = [getattr(model, n).register_forward_hook(
+            lambda m, i, o, n=n: sums.__setitem__(n, sums.get(n, 0) + o.detach().double().sum(dim=(0, 2, 3)) / (o.shape[2] * o.shape[3])))
+            for n in BLOCKS]
+        for a in range(0, len(idx), 16):                       # the script's loop (:173-189) over the pinned windows
+            b = torch.stack([ds[int(i)] for i in idx[a:a + 16]])
+            with torch.no_grad():
+                logits.append(model(b))
+            count += b.shape[0]
+        for h in hooks:
+            h.remove()
+        logits = torch.cat(logits)
+        prob = torch.nn.functional.softmax(logits, dim=1)[:, 1].numpy().astype(np.float32)
+        prob[plane.reshape(-1)[idx] == -9999] = -9999
+        c = FILLED[key]
+        out.update({key + "_gen": np.array(c["gen"]), key + "_H": c["H"], key + "_W": c["W"], key + "_seed": c["seed"],
+                    key + "_block": np.array(c["block"]), key + "_nodata": np.array(c["nodata"], np.int64).reshape(-1, 2),
+                    key + "_sha256": np.array(hashlib.sha256(plane.tobytes()).hexdigest()),
+                    key + "_idx": idx, key + "_kind": kind, key + "_logits": logits.numpy(), key + "_prob": prob})
+        for n in BLOCKS:
+            out[key + "_act_mean_" + n] = (sums[n] / count).float().numpy()   # per-channel mean over the pinned windows
+        v = prob != -9999
+        mid = (prob[v] > 1e-3) & (prob[v] < 1 - 1e-3)
+        print(key, plane.shape, "windows", len(idx), "p range %.4g .. %.4g" % (prob[v].min(), prob[v].max()),
+              "unsaturated %.1f %%" % (100 * mid.mean()), "mean |act| conv1 %.3g inception5b %.3g" % (
+                  float(np.abs(out[key + "_act_mean_conv1"]).mean()), float(np.abs(out[key + "_act_mean_inception5b"]).mean())))
+    out["versions"] = np.array("torch %s numpy %s" % (torch.__version__, np.__version__))
+    np.savez_compressed(os.path.join(HERE, "cnn_googlenet_filled_golden.npz"), **out)
+
+
 if __name__ == "__main__":
-    main()
+    main_filled() if "--filled" in sys.argv[1:] else main()

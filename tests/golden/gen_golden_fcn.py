@@ -2,7 +2,8 @@
 """Golden vectors of the reference's FCN shift-and-stitch fast mode (cnn/fcn_pred_pipeline.py), made with the REAL
 reference classes (development container only).
 
-    python tests/golden/gen_golden_fcn.py
+    python tests/golden/gen_golden_fcn.py            # cnn_fcn_golden.npz: a 45 x 70 plane, smaller than one window
+    python tests/golden/gen_golden_fcn.py --filled   # cnn_fcn_filled_golden.npz: a 160 x 192 plane full of data
 
 Same stand-ins as gen_golden_cnn.py (torchvision.transforms / rasterio are absent here).  ``FlightlineShiftStitch`` and
 ``stitch_stack`` run unmodified; the script's ``__main__`` needs a weights file next to the read-only reference, so
@@ -19,7 +20,7 @@ from torch import nn
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import gen_golden_cnn as GC  # noqa: E402
-from srcfinder_amd.cnn_weights import synthetic_plane, synthetic_state_dict  # noqa: E402
+from srcfinder_amd.cnn_weights import synthetic_filled_plane, synthetic_plane, synthetic_state_dict  # noqa: E402
 
 
 def main():
@@ -46,9 +47,14 @@ def main():
 
     mean, std = 110.6390, 183.9152          # COVID_QC, fcn_pred_pipeline.py:175-182
     tf = Compose([F.ClampCH4(vmin=0, vmax=4000), Normalize([mean], [std])])
-    H, W, scale = 45, 70, 32
-    plane = synthetic_plane(H, W, seed=77)
-    plane[3:6, 10:14] = -9999.0
+    filled = "--filled" in sys.argv[1:]
+    if filled:                              # larger than one 256 x 256 window, data everywhere (cnn_weights.synthetic_filled_plane)
+        H, W, scale, seed = 160, 192, 32, 78
+        plane = synthetic_filled_plane(H, W, seed=seed)
+    else:
+        H, W, scale, seed = 45, 70, 32, 77
+        plane = synthetic_plane(H, W, seed=seed)
+        plane[3:6, 10:14] = -9999.0
     GC.PLANE["mem://fcn"] = plane
     ds = F.FlightlineShiftStitch("mem://fcn", transform=tf, scale=scale)
     loader = torch.utils.data.DataLoader(ds, batch_size=16, shuffle=False, num_workers=0)
@@ -66,7 +72,8 @@ def main():
     # one shifted canvas and its raw prediction map, for the unit test of the prepare kernel / the trunk
     (t5, l5), canvas = ds[5 * scale + 9]
     print("stack", allpred.shape, "saliency", out.shape, "range", out[out != -9999].min(), out.max())
-    np.savez_compressed(os.path.join(HERE, "cnn_fcn_golden.npz"), seed_weights=2024, seed_plane=77, H=H, W=W, scale=scale,
+    np.savez_compressed(os.path.join(HERE, "cnn_fcn_filled_golden.npz" if filled else "cnn_fcn_golden.npz"), seed_weights=2024,
+                        seed_plane=seed, H=H, W=W, scale=scale,
                         mean=mean, std=std, plane=plane, saliency=out, predstack=allpred.astype(np.float32),
                         canvas_5_9=canvas.numpy()[0], versions=np.array("torch %s numpy %s" % (torch.__version__, np.__version__)))
 

@@ -324,6 +324,10 @@ def test_shared_trunk_rebuilds_its_maps_across_strips_at_flightline_width(net):
     assert info["shared_batches"] == info["batches"] >= -(-(r1 - r0) * W // batch) and info["rescued_batches"] == 0
     assert torch.equal(a, b)
     assert float(a[:r0].abs().sum()) == 0.0 and float(a[r1:].abs().sum()) == 0.0
+    # anchored to the reference arithmetic (not only to the other route): interior windows on both sides of the map rebuilds
+    idx = [505 * W + 130, 640 * W + 301, 777 * W + 468, 850 * W + 200, 903 * W + 377, 971 * W + 129]
+    want = O.predict_plane(plane, synthetic_state_dict(seed=2024), MEAN, STD, indices=idx)
+    _p_error(a.reshape(-1)[idx].cpu().numpy(), want, "flightline-width strip")
     # the call above scored two halves of the rows concurrently on two streams (cnn.LANES); one stream gives the same bits
     i1 = {}
     c = cnn.predict_flightline(plane, (MEAN, STD), net=net, batch=batch, rows=(r0, r1), route="split", info=i1, lanes=1)
@@ -624,6 +628,98 @@ def test_fp16_option_is_close_but_separate(gold):
 
 
 # ---- FCN shift-and-stitch (the reference's approximate fast mode, cnn/fcn_pred_pipeline.py) -------------------------
+# --- windows full of data (tests/golden/gen_golden_cnn.py --filled, cnn_googlenet_filled_golden.npz): the flightline case.  The
+# goldens above are planes smaller than a window (>= 98 % padding); the tests on large planes compare routes with each other only.
+# Bar: relative 1e-4 on p AND on 1 - p (a window at p = 0.99 must not pass at any error), NODATA placement exact.
+
+@pytest.fixture(scope="module")
+def filled(golden_dir):
+    return np.load(os.path.join(golden_dir, "cnn_googlenet_filled_golden.npz"))
+
+
+def _filled_plane(g, key):
+    from srcfinder_amd import cnn_weights
+    plane = getattr(cnn_weights, str(g[key + "_gen"]))(int(g[key + "_H"]), int(g[key + "_W"]), seed=int(g[key + "_seed"]))
+    for r, c in g[key + "_nodata"]:
+        plane[r, c] = -9999.0
+    return plane
+
+
+def _p_error(got, want, what):
+    """max |d| / min(p, 1 - p) over the data windows; asserts NODATA placement and |d| <= 1e-4 min(p, 1 - p) + 1e-7."""
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    assert np.array_equal(got == -9999, want == -9999), what
+    v = want != -9999
+    d, m = np.abs(got[v] - want[v]), np.minimum(want[v], 1 - want[v])
+    worst = float((d / m).max())
+    assert np.all(d <= 1e-4 * m + 1e-7), (what, worst, int(np.argmax(d / m)))
+    return worst
+
+
+@pytest.mark.parametrize("route", ["split", "split_conv3", "split_unshared", "winograd", "direct"])
+def test_every_route_against_the_reference_on_filled_windows(filled, net, route):
+    """sf_cnn_score_rows on each route against the filled golden.  Shared routes: ALL rows of a plane in one call, default lanes (2:
+    the lane cut falls inside the plane), batch 512 -- plane A (1400 rows) rebuilds its phase maps in both lanes and its pinned block
+    straddles a strip-map rebuild; every batch must have run on the shared trunk with none rescued, so no fallback passes unseen.
+    Unshared routes: the rows that hold the pinned windows."""
+    errs = {}
+    for key in ("A", "B"):
+        plane, idx = _filled_plane(filled, key), filled[key + "_idx"]
+        H, W = plane.shape
+        out = np.zeros(H * W, np.float32)
+        if route in ("split", "split_conv3"):
+            info = {}
+            out = cnn.predict_flightline(plane, (MEAN, STD), net=net, batch=512, route=route, info=info, to_numpy=True).reshape(-1)
+            assert info["shared_batches"] == info["batches"] >= -(-H * W // 512) and info["rescued_batches"] == 0, (key, info)
+        else:
+            rows = sorted(set((idx // W).tolist()))
+            runs, r0 = [], rows[0]
+            for a, b in zip(rows, rows[1:] + [None]):
+                if b != a + 1:
+                    runs.append((r0, a + 1))
+                    r0 = b
+            for rr in runs:
+                got = cnn.predict_flightline(plane, (MEAN, STD), net=net, batch=512, rows=rr, route=route, to_numpy=True)
+                out[rr[0] * W:rr[1] * W] = got.reshape(-1)[rr[0] * W:rr[1] * W]
+        errs[key] = _p_error(out[idx], filled[key + "_prob"], (route, key))
+    print("filled golden, route %s: max |dp| / min(p, 1-p) = A %.2e, B %.2e" % (route, errs["A"], errs["B"]))
+
+
+def test_python_sequenced_graph_and_its_taps_on_filled_windows(filled, net):
+    """forward_tiles (the same kernels sequenced from Python, split operands at the plane's calibrated scales) on every pinned window:
+    probabilities at the bar above, and per-layer channel means of the taps against the reference's (1e-4 relative)."""
+    import torch
+    keep = list(net.ascale)
+    try:
+        for key in ("A", "B"):
+            plane, idx = _filled_plane(filled, key), filled[key + "_idx"]
+            W = plane.shape[1]
+            ds = cnn.FlightlineConvolve(plane, (MEAN, STD), device=net.device)
+            net.calibrate(ds, 64)
+            out = torch.zeros(plane.size, dtype=torch.float32, device=net.device)
+            runs, a = [], 0                                  # consecutive window indices: one forward_tiles call each
+            for b in range(1, len(idx) + 1):
+                if b == len(idx) or idx[b] != idx[b - 1] + 1:
+                    runs.append((int(idx[a]), b - a))
+                    a = b
+            sums = {}
+            for t0, n in runs:
+                taps = {}
+                net.forward_tiles(ds.x, W, t0, n, plane=ds.plane, out=out, taps=taps, route="split")
+                for name, t in taps.items():                  # NHWC
+                    sums[name] = sums.get(name, 0) + t.double().mean(dim=(1, 2)).sum(0)
+            err = _p_error(out.cpu().numpy()[idx], filled[key + "_prob"], ("forward_tiles", key))
+            layer = {}
+            for name, t in sums.items():
+                got, want = (t / len(idx)).cpu().numpy(), filled[key + "_act_mean_" + name].astype(np.float64)
+                layer[name] = float((np.abs(got - want) / (np.abs(want) + 1e-1)).max())
+                np.testing.assert_allclose(got, want, rtol=1e-4, atol=1e-5, err_msg="%s %s" % (key, name))
+            print("filled golden %s, forward_tiles: p %.2e; per layer max |d| / (|mean| + 0.1): %s" % (
+                key, err, " ".join("%s %.1e" % kv for kv in layer.items())))
+    finally:
+        net.ascale = keep
+
+
 @pytest.fixture(scope="module")
 def fcn_gold(golden_dir):
     return np.load(os.path.join(golden_dir, "cnn_fcn_golden.npz"))
@@ -713,3 +809,21 @@ def test_fcn_fp16_option_is_close_but_separate(fcn_gold):
     assert d.max() < 0.5 and np.median(d) < 0.05, (d.max(), np.median(d))
     assert np.abs(sal[v] - want[v]).max() > 0                     # it really is a different arithmetic
     assert np.mean((sal[v] > 0.5) == (want[v] > 0.5)) > 0.99      # same side of the decision threshold almost everywhere
+
+
+def test_fcn_on_a_filled_plane_larger_than_a_window(golden_dir, net):
+    """The FCN fast mode on a 160 x 192 plane full of data (gen_golden_fcn.py --filled), on the split and the Winograd routes, at the
+    bars of test_fcn_shift_and_stitch_matches_reference."""
+    g = np.load(os.path.join(golden_dir, "cnn_fcn_filled_golden.npz"))
+    want = g["saliency"]
+    v = want != -9999
+    mid = v & (want > 1e-3) & (want < 1 - 1e-3)
+    assert mid.sum() > 5000
+    for route in ("split", "winograd"):
+        sal = cnn.fcn_predict_flightline(g["plane"], "COVID_QC", net=net, batch=16, to_numpy=True, route=route)
+        assert np.array_equal(sal == -9999, want == -9999), route
+        np.testing.assert_allclose(sal[v], want[v], rtol=5e-3, atol=2e-6, err_msg=route)
+        d = np.abs(_logit(sal[mid]) - _logit(want[mid]))
+        print("filled FCN golden, route %s: max |d logit| %.2e (median %.2e), max |dp| %.2e" % (
+            route, d.max(), np.median(d), np.abs(sal[v] - want[v]).max()))
+        assert d.max() < 5e-3, (route, d.max())
