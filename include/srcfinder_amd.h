@@ -438,9 +438,9 @@ int sf_cnn_head(const float *in, int ntiles, int HW, int C, const float *fcw, co
  * NODATA, plane may be NULL).  blob: the BatchNorm-folded float32 weights in ONE array of sf_cnn_blob_floats() values:
  * for conv1, conv2, conv3, then per inception block {branch1|branch2.0|branch3.0 stacked, branch2.1, branch3.1,
  * branch4.1}, then fc: weights [Cout][k*k][Cin] followed by the bias [Cout].  workspace >=
- * sf_cnn_score_workspace_bytes(batch) (activations of one batch + the Winograd / split-operand forms of the weights + the overflow
- * slots).  All launches are enqueued on `stream`.
- * route (an ARGUMENT of the call -- nothing process- or thread-wide selects the arithmetic):
+ * sf_cnn_score_workspace_bytes(batch, H, W, route) (activations of one batch + the Winograd / split-operand forms of the weights + the
+ * overflow slots + the trunk-sharing buffers of the route).  All launches are enqueued on `stream`.
+ * route (an ARGUMENT of the call -- nothing process- or thread-wide selects the arithmetic; one table in csrc/cnn_driver.hip):
  *   0  operand splitting on the fp16 matrix cores (sf_cnn_conv_split: the float32 tolerance class; the product's default) with the
  *      trunk through inception3b SHARED between the overlapping windows (below: sf_cnn_ring_pool1 ...; since the second half of round 6
  *      also the ring rows that see only a window's top / bottom padding, from strip maps the call builds per 16 image rows -- the
@@ -454,12 +454,13 @@ int sf_cnn_head(const float *in, int ntiles, int HW, int C, const float *fcw, co
  *      that raised its slot is scored AGAIN on route 4 before the call returns (info, if given: int[2] -- [0] the batches scored again,
  *      [1] the batches that ran on the shared trunk; a strip whose phase maps leave float16's range runs unshared).  The call
  *      therefore synchronises `stream` before returning on this route;
- *   4  Winograd F(2 x 2, 3 x 3) + fp32 implicit GEMM on the fp32 matrix cores;   2 (1)  the direct fp32 kernel for everything.
+ *   4  Winograd F(2 x 2, 3 x 3) + fp32 implicit GEMM on the fp32 matrix cores;   2 (1)  the direct fp32 kernel for everything
+ *      (1 runs 2's code: the pointer-form tile loads are chosen by sf_debug_set(17, 1) alone).
  * sf_cnn_calibrate: the scales alone (host array of sf_cnn_num_scales() floats: [0] maxpool1's output, [1] conv2's output,
  * [2 + 3 i ...] inception block i's input, its 3 x 3 reducer's output, its "5 x 5" reducer's output); synchronises `stream`. */
 size_t sf_cnn_blob_floats(void);
-size_t sf_cnn_score_workspace_bytes(int batch, int H, int W);   /* H = W = 0: without the trunk-sharing buffers (routes 3, 4, 2, 1; sf_cnn_calibrate);
-                                                                  else enough for either sharing route (0, 5) on an H x W plane */
+size_t sf_cnn_score_workspace_bytes(int batch, int H, int W, int route);   /* exactly what sf_cnn_score_rows checks for `route` on an
+                                                    H x W plane; H = W = 0 (sf_cnn_calibrate, any route): no trunk-sharing buffers; 0: bad argument */
 int sf_cnn_num_scales(void);
 int sf_cnn_calibrate(const float *padded, int H, int W, const float *blob, int batch, void *workspace, size_t workspace_bytes,
                      float *scales, void *stream);

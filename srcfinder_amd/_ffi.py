@@ -67,7 +67,7 @@ SIGNATURES = {
                                  vp, i32, i32, vp]),
     "sf_cnn_head": (i32, [vp, i32, i32, i32, vp, vp, vp, i64, f32, vp, vp]),
     "sf_cnn_blob_floats": (sz, []),
-    "sf_cnn_score_workspace_bytes": (C.c_size_t, [i32, i32, i32]),
+    "sf_cnn_score_workspace_bytes": (C.c_size_t, [i32, i32, i32, i32]),
     "sf_cnn_score_rows": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, sz, vp]),
     "sf_cnn_fcn_prepare": (i32, [vp, i32, i32, f32, f32, f32, f32, i32, i32, i32, i32, i32, vp, vp]),
     "sf_cnn_conv1_image": (i32, [vp, i32, i32, i32, vp, vp, vp, i32, vp]),

@@ -16,6 +16,7 @@ Every operator runs in a hand-written HIP kernel behind ``libsrcfinder_amd.so``;
 from __future__ import annotations
 
 import ctypes as C
+import functools
 
 import numpy as np
 
@@ -28,7 +29,8 @@ MODEL_NORM = {
 }
 BN_EPS = 0.001          # googlenet1.py:270
 NODATA = -9999.0
-# The convolutions' arithmetic routes (all float32 in / float32 accumulate; include/srcfinder_amd.h: sf_cnn_score_rows).
+# The convolutions' arithmetic routes (all float32 in / float32 accumulate): the codes of sf_cnn_score_rows, defined by ONE table
+# (ROUTE in csrc/cnn_driver.hip; _splits / _shares below).
 # "split": operand splitting on the fp16 matrix cores; through the C driver (sf_cnn_score_rows: whole image rows) with the trunk through
 # inception3b SHARED between the overlapping windows (csrc/cnn_share.hip); sequenced from Python one batch at a time (forward_tiles)
 # every window on its own -- "split_unshared" names that form on both drivers; "split_conv3": the sharing stops behind conv3 (round
@@ -131,8 +133,52 @@ class FlightlineConvolve(object):
 def _knob(key):
     """The calling thread's value of a tuning knob of the library (sf_debug_set)."""
     v = C.c_int(0)
-    _ffi.lib().sf_debug_get(int(key), C.byref(v))
+    _ffi.check(_ffi.lib().sf_debug_get(int(key), C.byref(v)), "sf_debug_get")
     return v.value
+
+
+def _on_threads(n, work):
+    """``work(i)`` for i < n, each on a host thread of its own that first takes over the calling thread's CNN tuning knobs
+    (sf_debug_set keys 16-18: the library keeps them per calling thread); a worker's exception is raised in the caller."""
+    import threading
+    knobs, errs = [(key, _knob(key)) for key in (16, 17, 18)], [None] * n
+
+    def run(i):
+        try:
+            for key, v in knobs:
+                _ffi.lib().sf_debug_set(key, v)
+            work(i)
+        except Exception as e:
+            errs[i] = e
+    threads = [threading.Thread(target=run, args=(i,)) for i in range(n)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    for e in errs:
+        if e is not None:
+            raise e
+
+
+def _route_code(route, half):
+    """The code of ``route`` (a name of ROUTES or a code).  None: 0 (operand splitting, the default) on the fp16 network, else the calling
+    thread's tuning knob 17 (tools)."""
+    if route is None:
+        return 0 if half else _knob(17)
+    r = ROUTES.get(route, route) if isinstance(route, str) else int(route)
+    if r not in ROUTES.values():
+        raise ValueError("route must be one of %r or 0 / 5 / 3 / 4 / 2 / 1" % (sorted(ROUTES),))
+    return r
+
+
+def _splits(code, half=False):
+    """Route ``code`` splits operands: per-layer activation scales and per-batch overflow slots apply (never on the fp16 network)."""
+    return not half and code in (ROUTES["split"], ROUTES["split_conv3"], ROUTES["split_unshared"])
+
+
+def _shares(code):
+    """Route ``code`` shares the trunk between overlapping windows (the C driver; the Python-sequenced graph never does)."""
+    return code in (ROUTES["split"], ROUTES["split_conv3"])
 
 
 def _pool_out(n, k, s, p):
@@ -167,7 +213,11 @@ class GoogLeNetHIP(object):
         # calibrate() has seen a plane; predict_flightline calibrates on every plane it scores
         self.ascale = [1.0] * int(_ffi.lib().sf_cnn_num_scales())
         self.route = None         # None: the calling thread's sf_debug_set(17, .) (0 unless a tool set it); else ROUTES / a code
-        self._route, self._flag = 0, None      # (state of the forward pass in progress)
+        self.c_driver = True      # False: score_tiles / predict_flightline sequence the kernels from Python (forward_tiles; the tests)
+        self.fuse_conv1 = True    # False: forward_tiles runs conv1 and maxpool1 as two kernels (tools/bench_cnn.py --no-fuse)
+        self.last_batches, self.last_shared_batches = None, 0    # the last C-driver call's batches, and those on the shared trunk
+        self._blob, self._lane_streams = None, None              # (built on first use: packed_blob, _score_rows_c's lanes)
+        self._split, self._wino, self._flag = False, False, None   # (the forward pass in progress)
         if state_dict is not None:
             self.load_state_dict(state_dict)
 
@@ -235,7 +285,7 @@ class GoogLeNetHIP(object):
         torch = _torch()
         if self.half:
             raise ValueError("the C driver scores in fp32")
-        if getattr(self, "_blob", None) is None:
+        if self._blob is None:
             parts = []
             for name in ("conv1", "conv2", "conv3"):
                 parts += [self.w[name][0].reshape(-1), self.w[name][1]]
@@ -261,15 +311,8 @@ class GoogLeNetHIP(object):
 
     # -- the convolutions' route and the split-operand route's range contracts --------------------------------
     def _route_code(self, route=None):
-        """0 operand splitting (fp16 matrix cores, fp32 tolerance class; default), 4 Winograd + fp32 matrix cores, 2 / 1 the direct
-        fp32 kernel.  An explicit argument wins, then ``self.route``, then the calling thread's tuning knob 17 (tools)."""
-        r = self.route if route is None else route
-        if r is None:
-            return 0 if self.half else _knob(17)
-        r = ROUTES.get(r, r) if isinstance(r, str) else int(r)
-        if r not in (0, 1, 2, 3, 4, 5):
-            raise ValueError("route must be one of %r or 0 / 5 / 3 / 4 / 2 / 1" % (sorted(ROUTES),))
-        return r
+        """The route code (module :func:`_route_code`): an explicit argument wins, then ``self.route``, then knob 17."""
+        return _route_code(self.route if route is None else route, self.half)
 
     def overflow_slots(self, n):
         """``n`` zeroed device ints for ``forward_tiles(..., overflow=slots[i:i+1])``: one per batch, read once at the end."""
@@ -285,7 +328,7 @@ class GoogLeNetHIP(object):
         L = _ffi.lib()
         H, W = ds.inshape[1], ds.inshape[2]
         with torch.cuda.device(self.device):
-            wsb = L.sf_cnn_score_workspace_bytes(int(batch), 0, 0)
+            wsb = L.sf_cnn_score_workspace_bytes(int(batch), 0, 0, ROUTES["winograd"])
             ws = self._buf("c_driver_ws", ((wsb + 3) // 4,))
             sc = (C.c_float * len(self.ascale))()
             _ffi.check(L.sf_cnn_calibrate(_ffi.ptr(ds.x), H, W, _ffi.ptr(self.packed_blob()), int(batch), _ffi.ptr(ws),
@@ -293,24 +336,25 @@ class GoogLeNetHIP(object):
         self.ascale = [float(v) for v in sc]
         return self.ascale
 
-    def _begin(self, route, overflow):
-        """Set the pass's route and overflow slot; returns True when this call owns the slot (and must check it itself)."""
+    def _begin(self, code, overflow):
+        """Set the pass's arithmetic and overflow slot (the Python-sequenced graph runs every split route unshared)."""
         torch = _torch()
-        self._route = self._route_code(route)
-        if self._route in (3, 5):
-            self._route = 0        # (the Python-sequenced graph always evaluates every window on its own)
-        own = False
-        if self._route == 0 and not self.half:
-            if overflow is None:
-                if getattr(self, "_own_flag", None) is None:
-                    self._own_flag = torch.zeros(1, dtype=torch.int32, device=self.device)
-                self._own_flag.zero_()
-                overflow, own = self._own_flag, True
+        self._split, self._wino = _splits(code, self.half), code == ROUTES["winograd"]
+        if self._split:
             same = overflow.is_cuda and (self.device.index is None or overflow.device.index == self.device.index)
             if overflow.dtype != torch.int32 or overflow.numel() < 1 or not same:
                 raise ValueError("overflow must be an int32 tensor on the network's device")
         self._flag = overflow
-        return own
+
+    def _rescued(self, fwd, code, out, what):
+        """``fwd(out=, route=, overflow=)`` on a split route without the caller's slot: :func:`_run_batches` over this one batch (a slot
+        of its own, read here -- one host synchronisation -- and the pass again on the fp32 matrix cores when it is up)."""
+        box = [out]
+
+        def one(_i, rt, slot):
+            box[0] = fwd(out=box[0], route=rt, overflow=slot)
+        _run_batches(self, code, 1, one, what)
+        return box[0]
 
     # -- operators -------------------------------------------------------------------------------------------
     def _conv(self, x, name, out, ch_off, a_in=1.0, a_out=1.0):
@@ -319,8 +363,7 @@ class GoogLeNetHIP(object):
         N, H, W, ldi = x.shape
         cout, taps, cin = w.shape
         k = 3 if taps == 9 else 1
-        mode = self._route
-        if mode == 0 and name in self.split:
+        if self._split and name in self.split:
             # tensors only split-operand convolutions read travel in the split format (csrc/cnn_split.hip): conv2's output, and the
             # 3 x 3 reducers' outputs that _inception's split3 call leaves in t2 / t3 -- scaled by their consumer's activation scale
             hi, lo, sc = self.split[name]
@@ -331,7 +374,7 @@ class GoogLeNetHIP(object):
                                            _ffi.ptr(self._flag), _ffi.stream_ptr()),
                        "sf_cnn_conv_split(%s)" % name)
             return
-        if k == 3 and self.winograd and name in self.wino and L.sf_cnn_wino_ok(H, W, cin) and mode == 4:
+        if k == 3 and self.winograd and name in self.wino and L.sf_cnn_wino_ok(H, W, cin) and self._wino:
             _ffi.check(L.sf_cnn_conv3x3_wino(_ffi.ptr(x), N, H, W, cin, ldi, _ffi.ptr(self.wino[name]), _ffi.ptr(b), cout,
                                              _ffi.ptr(out), out.shape[3], ch_off, _ffi.stream_ptr()), "sf_cnn_conv3x3_wino(%s)" % name)
             return
@@ -350,7 +393,7 @@ class GoogLeNetHIP(object):
 
     def _inception(self, x, spec, blk=0):
         name, cin, c1, c3r, c3, c5r, c5, pp = spec
-        split = not self.half and self._route == 0
+        split = self._split
         ax, a2, a3 = (self.ascale[2 + 3 * blk], self.ascale[3 + 3 * blk], self.ascale[4 + 3 * blk]) if split else (1.0, 1.0, 1.0)
         N, H, W, _ = x.shape
         y = self._buf(name + ".y", (N, H, W, c1 + c3 + c5 + pp))
@@ -394,7 +437,7 @@ class GoogLeNetHIP(object):
         """maxpool1 .. inception5b on the conv1 activations a1 [N, H, W, 64] (googlenet1.py:61-86); with ``pooled`` a1 is
         already the output of maxpool1 (the fused conv1 + pool kernel of the tile scorer)."""
         x = a1 if pooled else self._pool(a1, "pool1", 3, 2, 0)
-        split = not self.half and self._route == 0
+        split = self._split
         s0, s1 = (self.ascale[0], self.ascale[1]) if split else (1.0, 1.0)
         a3 = self._buf("conv2", x.shape)
         self._conv(x, "conv2", a3, 0, a_in=s0, a_out=s1)
@@ -418,8 +461,11 @@ class GoogLeNetHIP(object):
         torch = _torch()
         L = _ffi.lib()
         N, Hc, Wc = canvas.shape
+        code = self._route_code(route)
+        if overflow is None and _splits(code, self.half):
+            return self._rescued(functools.partial(self.forward_fcn, canvas), code, out, "canvas batches")
         with torch.cuda.device(self.device):
-            own = self._begin(route, overflow)
+            self._begin(code, overflow)
             st = _ffi.stream_ptr()
             Ho, Wo = (Hc - 1) // 2 + 1, (Wc - 1) // 2 + 1
             a1 = self._buf("conv1", (N, Ho, Wo, 64))
@@ -433,9 +479,6 @@ class GoogLeNetHIP(object):
             _ffi.check(getattr(L, "sf_cnn_head" + self.sfx)(_ffi.ptr(x), n * hq * wq, 1, cc, _ffi.ptr(self.fcw),
                                                             _ffi.ptr(self.fcb), None, C.c_longlong(0), NODATA,
                                                             _ffi.ptr(out), st), "sf_cnn_head")
-            if own and int(self._flag.item()):
-                _overflow_warning("a canvas batch")
-                return self.forward_fcn(canvas, out=out, route=4)
         return out
 
     def forward_tiles(self, padded, width, tile0, ntiles, plane=None, out=None, taps=None, route=None, overflow=None):
@@ -451,11 +494,15 @@ class GoogLeNetHIP(object):
         torch = _torch()
         L = _ffi.lib()
         Hp, Wp = padded.shape[-2], padded.shape[-1]
+        code = self._route_code(route)
+        if overflow is None and _splits(code, self.half):
+            return self._rescued(functools.partial(self.forward_tiles, padded, width, tile0, ntiles, plane=plane, taps=taps), code, out,
+                                 "batches (tiles %d..%d)" % (tile0, tile0 + ntiles))
         with torch.cuda.device(self.device):
-            own = self._begin(route, overflow)
+            self._begin(code, overflow)
             st = _ffi.stream_ptr()
             w, b = self.w["conv1"]
-            if taps is None and not self.half and getattr(self, "fuse_conv1", True):
+            if taps is None and not self.half and self.fuse_conv1:
                 # production: conv1 and maxpool1 in one kernel, the 4 MB-per-tile conv1 activation never reaches HBM
                 a1 = self._buf("pool1", (ntiles, 64, 64, 64))
                 _ffi.check(L.sf_cnn_conv1_pool(_ffi.ptr(padded), Hp, Wp, width, C.c_longlong(tile0), ntiles, _ffi.ptr(w),
@@ -474,9 +521,6 @@ class GoogLeNetHIP(object):
             _ffi.check(getattr(L, "sf_cnn_head" + self.sfx)(_ffi.ptr(x), ntiles, H * W, Cc, _ffi.ptr(self.fcw),
                                                             _ffi.ptr(self.fcb), _ffi.ptr(plane), C.c_longlong(tile0),
                                                             NODATA, _ffi.ptr(out), st), "sf_cnn_head")
-            if own and int(self._flag.item()):
-                _overflow_warning("tiles %d..%d" % (tile0, tile0 + ntiles))
-                return self.forward_tiles(padded, width, tile0, ntiles, plane=plane, out=out, taps=taps, route=4)
         return out
 
 
@@ -486,13 +530,29 @@ def _overflow_warning(what):
                   "the fp32 matrix cores" % what)
 
 
+def _run_batches(net, code, n, run_one, what):
+    """The split routes' overflow contract for ``n`` batches sequenced from Python, asynchronously: ``run_one(i, route, slot)`` enqueues
+    batch i, ``slot`` a device int32 the kernels raise when an activation leaves float16's range.  One slot per batch, read ONCE after
+    the last; the raised batches run again on the fp32 matrix cores (route "winograd", no slot) with one warning.  Other routes: every
+    batch once, no slot.  Returns the number of batches run again."""
+    slots = net.overflow_slots(n) if _splits(code, net.half) else None
+    for i in range(n):
+        run_one(i, code, None if slots is None else slots[i:i + 1])
+    redo = [] if slots is None else [i for i, v in enumerate(slots.cpu().tolist()) if v]
+    for i in redo:
+        run_one(i, ROUTES["winograd"], None)
+    if redo:
+        _overflow_warning("%d of %d %s" % (len(redo), n, what))
+    return len(redo)
+
+
 def _score_rows_one(net, ds, r0, r1, batch, out, code, ws_key="c_driver_ws"):
     """ONE sf_cnn_score_rows call on image rows [r0, r1) on the calling thread's current stream; returns (re-scored, shared) batches."""
     torch = _torch()
     L = _ffi.lib()
     H, W = ds.inshape[1], ds.inshape[2]
     with torch.cuda.device(net.device):
-        wsb = L.sf_cnn_score_workspace_bytes(int(batch), H if code in (0, 5) else 0, W if code in (0, 5) else 0)
+        wsb = L.sf_cnn_score_workspace_bytes(int(batch), H, W, code)
         ws = net._buf(ws_key, ((wsb + 3) // 4,))
         nres = (C.c_int * 2)(0, 0)
         sc = (C.c_float * len(net.ascale))(*net.ascale)
@@ -517,45 +577,25 @@ def _score_rows_c(net, ds, r0, r1, batch, out, code, lanes=None):
     lanes = LANES if lanes is None else int(lanes)
     lanes = max(1, min(lanes, ((r1 - r0) * W) // (4 * int(batch))))
     net.last_batches = -(-(r1 - r0) * W // int(batch))         # batches the call launches (every lane's last one may be short)
-    if lanes == 1 or code not in (0, 3, 5):
+    if lanes == 1 or not _splits(code):
         nres = _score_rows_one(net, ds, r0, r1, batch, out, code)
     else:
-        import threading
-        L = _ffi.lib()
-        knobs = {}
-        for key in (16, 17, 18):                                # the library's tuning knobs are per calling thread
-            v = C.c_int(0)
-            _ffi.check(L.sf_debug_get(key, C.byref(v)), "sf_debug_get")
-            knobs[key] = v.value
         with torch.cuda.device(net.device):
             cur = torch.cuda.current_stream()
-            if getattr(net, "_lane_streams", None) is None or len(net._lane_streams) < lanes:
+            if net._lane_streams is None or len(net._lane_streams) < lanes:
                 net._lane_streams = [torch.cuda.Stream(device=net.device) for _ in range(lanes)]
             net.packed_blob()                                    # (built once, here, not by two threads at a time)
         cuts = [r0 + (r1 - r0) * i // lanes for i in range(lanes + 1)]
         net.last_batches = sum(-(-(cuts[i + 1] - cuts[i]) * W // int(batch)) for i in range(lanes))
-        res, errs = [None] * lanes, [None] * lanes
+        res = [None] * lanes
 
         def work(i):
-            try:
-                for key, v in knobs.items():
-                    L.sf_debug_set(key, v)
-                with torch.cuda.device(net.device):
-                    s = net._lane_streams[i]
-                    s.wait_stream(cur)                           # the plane and the weights were produced on the caller's stream
-                    with torch.cuda.stream(s):
-                        res[i] = _score_rows_one(net, ds, cuts[i], cuts[i + 1], batch, out, code, ws_key="c_driver_ws_lane%d" % i)
-            except Exception as e:                               # surfaced in the caller's thread
-                errs[i] = e
-
-        threads = [threading.Thread(target=work, args=(i,)) for i in range(lanes)]
-        for t in threads:
-            t.start()
-        for t in threads:
-            t.join()
-        for e in errs:
-            if e is not None:
-                raise e
+            with torch.cuda.device(net.device):
+                s = net._lane_streams[i]
+                s.wait_stream(cur)                               # the plane and the weights were produced on the caller's stream
+                with torch.cuda.stream(s):
+                    res[i] = _score_rows_one(net, ds, cuts[i], cuts[i + 1], batch, out, code, ws_key="c_driver_ws_lane%d" % i)
+        _on_threads(lanes, work)
         with torch.cuda.device(net.device):
             for s in net._lane_streams[:lanes]:
                 cur.wait_stream(s)
@@ -572,20 +612,14 @@ def score_tiles(net, ds, t_first, t_last, batch, out, route=None, lanes=None):
     batches are scored again on the fp32 matrix cores (cnn_pred_pipeline.py:173-181).  Returns the number of batches re-scored."""
     W = ds.inshape[2]
     code = net._route_code(route)
-    if not net.half and getattr(net, "c_driver", True) and t_first % W == 0 and t_last % W == 0 and t_last > t_first:
+    if not net.half and net.c_driver and t_first % W == 0 and t_last % W == 0 and t_last > t_first:
         return _score_rows_c(net, ds, t_first // W, t_last // W, batch, out, code, lanes)       # whole image rows: the C-side driver
     starts = list(range(int(t_first), int(t_last), int(batch)))
-    slots = net.overflow_slots(len(starts)) if (code in (0, 3, 5) and not net.half) else None
-    for i, t0 in enumerate(starts):
-        net.forward_tiles(ds.x, W, t0, min(batch, t_last - t0), plane=ds.plane, out=out, route=code,
-                          overflow=None if slots is None else slots[i:i + 1])
-    redo = [] if slots is None else [i for i, v in enumerate(slots.cpu().tolist()) if v]
-    for i in redo:
+
+    def one(i, rt, slot):
         t0 = starts[i]
-        net.forward_tiles(ds.x, W, t0, min(batch, t_last - t0), plane=ds.plane, out=out, route=4)
-    if redo:
-        _overflow_warning("%d of %d batches" % (len(redo), len(starts)))
-    return len(redo)
+        net.forward_tiles(ds.x, W, t0, min(batch, t_last - t0), plane=ds.plane, out=out, route=rt, overflow=slot)
+    return _run_batches(net, code, len(starts), one, "batches")
 
 
 def predict_flightline(cmf2d, model="COVID_QC", weights=None, batch=32, gpus=None, rows=None, net=None, to_numpy=False,
@@ -643,7 +677,7 @@ def predict_flightline(cmf2d, model="COVID_QC", weights=None, batch=32, gpus=Non
     r0, r1 = (0, H) if rows is None else rows
     code = net._route_code(route)
     rescued = 0
-    if code in (0, 3, 5) and not net.half:
+    if _splits(code, net.half):
         # ONE set of scales for the call, whichever driver sequences the graph: the caller's, or sf_cnn_calibrate on this plane
         if scales is not None:
             if len(scales) != len(net.ascale):
@@ -651,75 +685,44 @@ def predict_flightline(cmf2d, model="COVID_QC", weights=None, batch=32, gpus=Non
             net.ascale = [float(v) for v in scales]
         else:
             net.calibrate(ds, batch)
-    if not net.half and getattr(net, "c_driver", True):
+    if not net.half and net.c_driver:
         # the C-side driver sequences the whole graph for the row range: one library call (shared trunk, per-batch overflow slots
         # and the fp32 re-scoring of raised batches included)
         rescued = _score_rows_c(net, ds, r0, r1, batch, out, code, lanes) if r1 > r0 else 0
     else:
         rescued = score_tiles(net, ds, r0 * W, r1 * W, batch, out, route=code)
     if info is not None:
-        info.update(rescued_batches=rescued, route=code, scales=list(net.ascale) if code in (0, 3, 5) else None,
-                    shared_batches=getattr(net, "last_shared_batches", 0) if code in (0, 5) else 0,
-                    batches=getattr(net, "last_batches", None))
+        info.update(rescued_batches=rescued, route=code, scales=list(net.ascale) if _splits(code) else None,
+                    shared_batches=net.last_shared_batches if _shares(code) else 0, batches=net.last_batches)
     out = out.view(H, W)
     return out.cpu().numpy() if to_numpy else out
 
 
 def _predict_multi_gpu(cmf2d, model, weights, batch, gpus, to_numpy, precision, route=None, info=None, scales=None, lanes=None):
     """Row blocks of the saliency map on several GPUs of one process (one host thread per device)."""
-    import threading
     torch = _torch()
     if weights is None:
         raise ValueError("weights (a GoogLeNet state_dict) are required")
     plane = cmf2d.detach().cpu().numpy() if torch.is_tensor(cmf2d) else np.asarray(cmf2d, dtype=np.float32)
     H = plane.shape[0]
     n = len(gpus)
-    parts, errs, infos = [None] * n, [None] * n, [dict() for _ in range(n)]
-    # the library's tuning knobs are per calling thread: hand the caller's CNN knobs to the workers (the convolutions' route is
-    # resolved HERE, once, and passed to every worker as an argument)
-    route = GoogLeNetHIP._route_code(_RouteOnly(precision), route)
-    import ctypes
-    L = _ffi.lib()
-    knobs = {}
-    for key in (16, 17, 18):
-        v = ctypes.c_int(0)
-        _ffi.check(L.sf_debug_get(key, ctypes.byref(v)), "sf_debug_get")
-        knobs[key] = v.value
+    parts, infos = [None] * n, [dict() for _ in range(n)]
+    route = _route_code(route, precision == "fp16")       # (resolved HERE, once, and passed to every worker as an argument)
 
     def work(i):
-        try:
-            for key, v in knobs.items():
-                L.sf_debug_set(key, v)
-            dev = torch.device("cuda", gpus[i])
-            with torch.cuda.device(dev):
-                net = GoogLeNetHIP(weights, device=dev, precision=precision)
-                r0, r1 = i * H // n, (i + 1) * H // n
-                sal = predict_flightline(plane, model, net=net, batch=batch, rows=(r0, r1), route=route, info=infos[i], scales=scales,
-                                         lanes=lanes)
-                parts[i] = sal[r0:r1].to(torch.device("cuda", gpus[0]), non_blocking=False)
-        except Exception as e:                                  # surfaced in the caller's thread
-            errs[i] = e
-
-    threads = [threading.Thread(target=work, args=(i,)) for i in range(n)]
-    for t in threads:
-        t.start()
-    for t in threads:
-        t.join()
-    for e in errs:
-        if e is not None:
-            raise e
+        dev = torch.device("cuda", gpus[i])
+        with torch.cuda.device(dev):
+            net = GoogLeNetHIP(weights, device=dev, precision=precision)
+            r0, r1 = i * H // n, (i + 1) * H // n
+            sal = predict_flightline(plane, model, net=net, batch=batch, rows=(r0, r1), route=route, info=infos[i], scales=scales,
+                                     lanes=lanes)
+            parts[i] = sal[r0:r1].to(torch.device("cuda", gpus[0]), non_blocking=False)
+    _on_threads(n, work)
     if info is not None:
         info.update(rescued_batches=sum(d.get("rescued_batches", 0) for d in infos), route=route,
                     per_block_rescued=[d.get("rescued_batches", 0) for d in infos], scales=infos[0].get("scales"))
     out = torch.cat(parts, 0)
     return out.cpu().numpy() if to_numpy else out
-
-
-class _RouteOnly(object):
-    """(just enough of a network for GoogLeNetHIP._route_code before the per-device networks exist)"""
-
-    def __init__(self, precision):
-        self.route, self.half = None, precision == "fp16"
 
 
 def fcn_predict_flightline(cmf2d, model="COVID_QC", weights=None, scale=32, batch=8, net=None, to_numpy=False,
@@ -749,28 +752,20 @@ def fcn_predict_flightline(cmf2d, model="COVID_QC", weights=None, scale=32, batc
     code = net._route_code(route)
     with torch.cuda.device(net.device):
         st = _ffi.stream_ptr()
-        if code in (0, 3, 5) and not net.half:
+        if _splits(code, net.half):
             # the split route's activation scales: calibrated on this plane's 256 x 256 windows (the same trunk, the same statistics)
             net.calibrate(FlightlineConvolve(plane, (mean, std) if (vmin, vmax) == (0.0, 4000.0) else
                                              Compose([ClampCH4(int(vmin), int(vmax)), Normalize([mean], [std])]), device=net.device))
         canvas = torch.empty((batch, Hc, Wc), dtype=torch.float32, device=net.device)
         starts = list(range(s0, s1, batch))
-        slots = net.overflow_slots(len(starts)) if (code in (0, 3, 5) and not net.half) else None
 
-        def run(i, rt):
+        def run(i, rt, slot):
             a = starts[i]
             n = min(batch, s1 - a)
             _ffi.check(L.sf_cnn_fcn_prepare(_ffi.ptr(plane), H, W, float(vmin), float(vmax), float(mean), float(std), scale,
                                             a, n, Hc, Wc, _ffi.ptr(canvas), st), "sf_cnn_fcn_prepare")
-            pred = net.forward_fcn(canvas[:n], route=rt, overflow=None if (slots is None or rt not in (0, 3, 5)) else slots[i:i + 1])
+            pred = net.forward_fcn(canvas[:n], route=rt, overflow=slot)
             _ffi.check(L.sf_cnn_fcn_stitch(_ffi.ptr(pred), n, a, scale, pred.shape[1], pred.shape[2], _ffi.ptr(plane), H, W,
                                            NODATA, _ffi.ptr(out), st), "sf_cnn_fcn_stitch")
-
-        for i in range(len(starts)):
-            run(i, code)
-        redo = [] if slots is None else [i for i, v in enumerate(slots.cpu().tolist()) if v]
-        for i in redo:                               # the split-operand kernels' float16 range (see predict_flightline)
-            run(i, 4)
-        if redo:
-            _overflow_warning("%d of %d shift batches" % (len(redo), len(starts)))
+        _run_batches(net, code, len(starts), run, "shift batches")      # (the split kernels' float16 range: see predict_flightline)
     return out.cpu().numpy() if to_numpy else out

@@ -274,16 +274,25 @@ int prepare_wino(Net &N) {
 
 int build_strips(Net &N, const float *padded, int H, int W, int ra, const float *as);
 
-// One batch of windows through the eval graph (googlenet1.py:110-163) on the given route:
-//   0 operand splitting on the fp16 matrix cores (cnn_split.hip; `as`: the NSCALE activation scales, `flag`: this batch's overflow slot)
-//   4 Winograd F(2 x 2, 3 x 3) for the 3 x 3 layers where the geometry allows + the fp32 implicit GEMM (cnn_wino.hip / cnn_kernels.hip)
-//   2 the direct fp32 implicit GEMM for everything (1: its pointer-form tile loads, chosen inside sf_cnn_conv by sf_debug_set(17, 1))
-// amax != nullptr (routes 4 / 2): the largest magnitude of every tensor a split convolution would read is folded into amax[NSCALE]
-int run_batch(Net &N, const float *padded, const float *plane, int H, int W, long long tile0, int n, int route, const float *as, int *flag,
+// THE table of sf_cnn_score_rows' route codes (include/srcfinder_amd.h), indexed by the code: the trunk-sharing depth (0 none, 1 through
+// conv3, 2 through inception3b), operand splitting (activation scales and overflow slots apply), and the Form of an unshared batch in
+// run_batch -- operand splitting on the fp16 matrix cores (cnn_split.hip) with the trunk Shared to the depth make_net built, or every
+// window on its own (Split); Winograd F(2 x 2, 3 x 3) where the geometry allows + the fp32 implicit GEMM (Wino, cnn_wino.hip: also the
+// rescue and the calibration); the direct fp32 implicit GEMM (Direct).  Route 1 runs route 2's code: the direct kernel's pointer-form
+// tile loads are chosen inside sf_cnn_conv by sf_debug_set(17, 1) alone.
+enum class Form { Shared, Split, Wino, Direct };
+struct Route { int depth; bool split; Form form; };
+constexpr Route ROUTE[] = {{2, true, Form::Split}, {0, false, Form::Direct}, {0, false, Form::Direct},   // split, direct_pointer, direct
+                           {0, true, Form::Split}, {0, false, Form::Wino},   {1, true, Form::Split}};   // split_unshared, winograd, split_conv3
+const Route *route_of(int code) { return code >= 0 && code < int(sizeof ROUTE / sizeof *ROUTE) ? ROUTE + code : nullptr; }
+
+// One batch of windows through the eval graph (googlenet1.py:110-163).  Split forms: `as` the NSCALE activation scales, `flag` the
+// batch's overflow slot.  amax != nullptr (Wino / Direct): the largest magnitude of every tensor a split convolution reads -> amax[NSCALE]
+int run_batch(Net &N, const float *padded, const float *plane, int H, int W, long long tile0, int n, Form form, const float *as, int *flag,
               float *amax, float *out) {
   const int Hp = H + 255, Wp = W + 255;
-  const bool share = route == 0;             // 0: operand splitting with the trunk up to conv3 shared; 3: every window on its own
-  const bool use_split = route == 0 || route == 3, use_wino = route == 4;
+  const bool share = form == Form::Shared;
+  const bool use_split = share || form == Form::Split, use_wino = form == Form::Wino;
   void *stream = (void *)N.st;
   int rc = 0;
   auto conv3x3 = [&](const float *in, int hw, int cin, const Layer &l, size_t uoff, const SplitL &sl, int cout, float a_in, float *o, int ldo,
@@ -472,7 +481,7 @@ int run_batch(Net &N, const float *padded, const float *plane, int H, int W, lon
 // The phase maps for the image rows [r0, r0 + SH.rows) (clipped to the plane): per phase (r & 3, c & 3) the plane shifted by the
 // phase through conv1 (fully convolutional kernel) -> maxpool1 -> conv2 -> conv3, the last two by operand splitting with the
 // batch kernels' scales.  Synchronises the stream (the maps' own overflow slot is read): once per SHARE_ROWS image rows.
-// map_ok = false when an activation left float16's range: the strip's batches then run unshared (route 3).
+// map_ok = false when an activation left float16's range: the strip's batches then run unshared (Form::Split).
 int build_maps(Net &N, const float *padded, int H, int W, int r0, const float *as) {
   const Share &S = N.SH;
   const int Hp = H + 255, Wp = W + 255, Rb = (r0 >> 3) << 1;       // (an even canvas row: the 64-phase maps start on a multiple of 8)
@@ -622,7 +631,7 @@ int calibrate(Net &N, const float *padded, int H, int W, int batch, float *scale
     last = t0;
     for (int k = 0; k < per; k += batch) {
       const int n = (per - k < batch) ? per - k : batch;
-      if ((rc = run_batch(N, padded, nullptr, H, W, t0 + k, n, 4, nullptr, nullptr, N.amax, nullptr))) return rc;
+      if ((rc = run_batch(N, padded, nullptr, H, W, t0 + k, n, Form::Wino, nullptr, nullptr, N.amax, nullptr))) return rc;
     }
   }
   float mx[NSCALE];
@@ -653,18 +662,17 @@ extern "C" {
 
 size_t sf_cnn_blob_floats(void) { return blob_layout().total; }
 int sf_cnn_num_scales(void) { return NSCALE; }
-size_t sf_cnn_score_workspace_bytes(int batch, int H, int W) {
-  if (batch < 1) return 0;
-  // either sharing route's: depth 2 is usually the larger, but where no depth-2 strip fits under the pair limit (total 0) depth 1 still may
-  const size_t d1 = share_layout(batch, H, W, 1).total, d2 = share_layout(batch, H, W, 2).total;
-  return base_bytes(batch) + sf_align((d1 > d2 ? d1 : d2) * sizeof(float));
+// exactly what sf_cnn_score_rows checks: the base and the sharing buffers of the depth the route builds (none for H = W = 0)
+size_t sf_cnn_score_workspace_bytes(int batch, int H, int W, int route) {
+  const Route *R = route_of(route);
+  return batch < 1 || !R ? 0 : base_bytes(batch) + (R->depth ? sf_align(share_layout(batch, H, W, R->depth).total * sizeof(float)) : 0);
 }
 
 int sf_cnn_calibrate(const float *padded, int H, int W, const float *blob, int batch, void *workspace, size_t workspace_bytes,
                      float *scales, void *stream) {
   if (!padded || !blob || !workspace || !scales || H < 1 || W < 1 || batch < 1) { sf_set_error("sf_cnn_calibrate: bad argument"); return -1; }
-  if (workspace_bytes < sf_cnn_score_workspace_bytes(batch, 0, 0)) {
-    sf_set_error("sf_cnn_calibrate: workspace too small: need %zu bytes, got %zu", sf_cnn_score_workspace_bytes(batch, 0, 0), workspace_bytes);
+  if (workspace_bytes < base_bytes(batch)) {
+    sf_set_error("sf_cnn_calibrate: workspace too small: need %zu bytes, got %zu", base_bytes(batch), workspace_bytes);
     return -4;
   }
   Net N = make_net(blob, batch, workspace, stream);
@@ -673,36 +681,31 @@ int sf_cnn_calibrate(const float *padded, int H, int W, const float *blob, int b
 
 int sf_cnn_score_rows(const float *padded, const float *plane, int H, int W, int r0, int r1, const float *blob, float *out,
                       int batch, int route, const float *scales, int *info, void *workspace, size_t workspace_bytes, void *stream) {
-  if (!padded || !blob || !out || !workspace || H < 1 || W < 1 || r0 < 0 || r1 > H || r0 > r1 || batch < 1 ||
-      (route != 0 && route != 5 && route != 3 && route != 4 && route != 2 && route != 1)) {
+  const Route *R = route_of(route);
+  if (!padded || !blob || !out || !workspace || H < 1 || W < 1 || r0 < 0 || r1 > H || r0 > r1 || batch < 1 || !R) {
     sf_set_error("sf_cnn_score_rows: bad argument");
     return -1;
   }
-  const bool sharing = route == 0 || route == 5;       // 0: through inception3b (depth 2); 5: through conv3 (depth 1, round 6's first form)
-  const int depth = route == 0 ? 2 : 1;
-  // the layout this call builds (its depth), not sf_cnn_score_workspace_bytes' maximum: a caller that sized the workspace by it passes
-  const size_t need = base_bytes(batch) + (sharing ? sf_align(share_layout(batch, H, W, depth).total * sizeof(float)) : 0);
+  const size_t need = sf_cnn_score_workspace_bytes(batch, H, W, route);
   if (workspace_bytes < need) {
     sf_set_error("sf_cnn_score_rows: workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
     return -4;
   }
   if (info) info[0] = info[1] = 0;          // [0] batches scored again on the fp32 matrix cores, [1] batches that ran on the shared trunk
-  Net N = make_net(blob, batch, workspace, stream, sharing ? H : 0, sharing ? W : 0, depth, r0, r1, workspace_bytes);
+  Net N = make_net(blob, batch, workspace, stream, H, W, R->depth, r0, r1, workspace_bytes);     // (depth 0: no sharing buffers)
   const long long i0 = (long long)r0 * W, i1 = (long long)r1 * W;
   if (i0 >= i1) return 0;
   int rc = 0;
-  if (!sharing && route != 3) {
-    if (route == 4 && (rc = prepare_wino(N))) return rc;
-    for (long long tile0 = i0; tile0 < i1; tile0 += batch) {
-      const int n = (int)((i1 - tile0 < batch) ? (i1 - tile0) : batch);
-      if ((rc = run_batch(N, padded, plane, H, W, tile0, n, route, nullptr, nullptr, nullptr, out))) return rc;
-    }
-    return 0;
+  auto unsplit = [&](long long t0, Form form) {       // one batch without scales or overflow slot (the other routes; the rescue)
+    return run_batch(N, padded, plane, H, W, t0, (int)(i1 - t0 < batch ? i1 - t0 : batch), form, nullptr, nullptr, nullptr, out);
+  };
+  if (!R->split) {
+    if (R->form == Form::Wino && (rc = prepare_wino(N))) return rc;
+    for (long long tile0 = i0; tile0 < i1 && !rc; tile0 += batch) rc = unsplit(tile0, R->form);
+    return rc;
   }
-  // route 0: operand splitting with its two range contracts.  Underflow: the per-layer activation scales (the caller's, or a
-  // calibration pass over the plane).  Overflow: every batch owns a device flag; the flags are read back every NFLAG batches and
-  // the batches that raised theirs are scored again on the fp32 matrix cores -- so this route synchronises the stream before it
-  // returns, and what it returns is never silently wrong
+  // the split-operand routes' range contracts: the per-layer activation scales (the caller's, or calibrated on the plane) against
+  // underflow; a batch that raised its overflow slot (read back every NFLAG batches) is scored again as Form::Wino before the return
   float as[NSCALE];
   if (scales) {
     for (int i = 0; i < NSCALE; ++i) {
@@ -723,26 +726,23 @@ int sf_cnn_score_rows(const float *padded, const float *plane, int H, int W, int
     long long tile0 = group0;
     for (; tile0 < i1 && nb < NFLAG; tile0 += batch, ++nb) {
       const int n = (int)((i1 - tile0 < batch) ? (i1 - tile0) : batch);
-      int rt = 3;
-      if (sharing && N.share) {                // the phase maps must cover the batch's image rows
+      Form form = R->form;
+      if (N.share) {                           // the phase maps must cover the batch's image rows
         const int rf = (int)(tile0 / W), rl = (int)((tile0 + n - 1) / W);
         if (!(N.map_r0 >= 0 && N.map_r0 <= rf && rl < N.map_r1))
           if ((rc = build_maps(N, padded, H, W, rf, as))) return rc;
-        if (N.map_ok) rt = 0;
+        if (N.map_ok) form = Form::Shared;
         if (N.map_ok && info) ++info[1];
-        if (N.map_ok && N.SH.band && route == 0 && sf_tune().cnn_variant != 3 && !(N.strip_r0 >= 0 && N.strip_r0 <= rf && rl < N.strip_r0 + N.strip_nr))
+        if (N.map_ok && N.SH.band && sf_tune().cnn_variant != 3 && !(N.strip_r0 >= 0 && N.strip_r0 <= rf && rl < N.strip_r0 + N.strip_nr))
           if ((rc = build_strips(N, padded, H, W, rf, as))) return rc;
       }
-      if ((rc = run_batch(N, padded, plane, H, W, tile0, n, rt, as, N.flags + nb, nullptr, out))) return rc;
+      if ((rc = run_batch(N, padded, plane, H, W, tile0, n, form, as, N.flags + nb, nullptr, out))) return rc;
     }
     SF_HIP(hipMemcpyAsync(host_flags, N.flags, nb * sizeof(int), hipMemcpyDeviceToHost, N.st));
     SF_HIP(hipStreamSynchronize(N.st));
     for (int b = 0; b < nb; ++b) {
       if (!host_flags[b]) continue;
-      const long long t0 = group0 + (long long)b * batch;
-      const int n = (int)((i1 - t0 < batch) ? (i1 - t0) : batch);
-      if ((rc = prepare_wino(N))) return rc;
-      if ((rc = run_batch(N, padded, plane, H, W, t0, n, 4, nullptr, nullptr, nullptr, out))) return rc;
+      if ((rc = prepare_wino(N)) || (rc = unsplit(group0 + (long long)b * batch, Form::Wino))) return rc;
       if (info) ++info[0];
     }
     group0 = tile0;

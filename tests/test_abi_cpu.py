@@ -162,27 +162,30 @@ def test_tuning_knobs_refuse_retired_forms_and_stay_per_thread():
     assert seen == {"before": 0, "after": 4}
 
 
-def test_cnn_score_rows_workspace_contract_covers_every_sharing_route():
+def test_cnn_score_workspace_bytes_is_the_need_of_every_route():
     """sf_cnn_score_rows checks the workspace against the layout the call will build (route 0: the trunk shared through
-    inception3b, depth 2; route 5: through conv3, depth 1), and sf_cnn_score_workspace_bytes(batch, H, W) is enough for both.
-    Where no depth-2 strip fits under the 2 GB map + ring limit, depth 2 shares nothing but depth 1 still does: the depth-1
-    buffers must be counted (before, a workspace of the reported size was written past its end).  A 1-byte workspace: every
-    call returns -4 at the size check, before any device work, so the dummy pointers are never read."""
+    inception3b, depth 2; route 5: through conv3, depth 1; the others share nothing), and sf_cnn_score_workspace_bytes(batch, H, W,
+    route) reports exactly that need.  Where no depth-2 strip fits under the 2 GB map + ring limit, depth 2 shares nothing but depth 1
+    still does: the depth-1 buffers must be counted (before, a workspace of the reported size was written past its end).  A 1-byte
+    workspace: every call returns -4 at the size check, before any device work, so the dummy pointers are never read."""
     L = _ffi.lib()
     one = ctypes.c_void_p(16)
     H = 1000
     for batch in (64, 1024, 2048, 4096):
-        base = L.sf_cnn_score_workspace_bytes(batch, 0, 0)
+        base = L.sf_cnn_score_workspace_bytes(batch, 0, 0, 0)
         for W in (300, 598, 1242, 2400):
-            full = L.sf_cnn_score_workspace_bytes(batch, H, W)
-            assert full >= base
-            for route in (0, 5):
+            for route in (0, 5, 3, 4, 2, 1):
+                assert L.sf_cnn_score_workspace_bytes(batch, 0, 0, route) == base, (batch, route)
                 rc = L.sf_cnn_score_rows(one, one, H, W, 0, H, one, one, batch, route, None, None, one, 1, None)
                 msg = L.sf_last_error_string().decode()
                 assert rc == -4, (batch, W, route, rc, msg)
                 m = re.search(r"need (\d+) bytes, got 1\b", msg)
                 assert m, msg
                 need = int(m.group(1))
-                assert base <= need <= full, (batch, W, route, need, base, full)
+                assert need == L.sf_cnn_score_workspace_bytes(batch, H, W, route), (batch, W, route, need)
+                assert need >= base and (route in (0, 5) or need == base), (batch, W, route, need, base)
                 if (batch, W) in ((2048, 1242), (4096, 598)) and route == 5:
                     assert need > base, (batch, W, need, base)      # the depth-1 maps and rings are counted
+    for route in (-1, 6):                                           # not a route: no size, and the call refuses it
+        assert L.sf_cnn_score_workspace_bytes(64, H, 300, route) == 0
+        assert L.sf_cnn_score_rows(one, one, H, 300, 0, H, one, one, 64, route, None, None, one, 1, None) == -1

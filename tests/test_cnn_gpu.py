@@ -119,7 +119,7 @@ def test_fused_conv1_pool_matches_the_two_kernels(net):
     assert float(p_ref.max()) > 0          # ReLU outputs: something is active
 
 
-def test_c_driver_equals_the_python_sequenced_graph(gold):
+def test_c_driver_equals_the_python_sequenced_graph_at_route_sized_workspaces(gold):
     """sf_cnn_score_rows (the whole graph for a row range in one C call, weights as one packed blob) against the same
     kernels sequenced from Python (forward_tiles): bit-identical saliency maps, row ranges and ragged last batches."""
     import torch
@@ -141,8 +141,9 @@ def test_c_driver_equals_the_python_sequenced_graph(gold):
     e = cnn.predict_flightline(plane, (MEAN, STD), net=net, batch=64, rows=(3, 8))
     assert torch.equal(e[3:8], d[3:8]) and float(e[:3].abs().sum()) == 0.0
     L = _ffi.lib()
-    assert net.packed_blob().numel() == L.sf_cnn_blob_floats() and L.sf_cnn_score_workspace_bytes(13, 0, 0) > 0
-    assert L.sf_cnn_score_workspace_bytes(13, 11, 7) > L.sf_cnn_score_workspace_bytes(13, 0, 0)
+    assert net.packed_blob().numel() == L.sf_cnn_blob_floats() and L.sf_cnn_score_workspace_bytes(13, 0, 0, 0) > 0
+    assert L.sf_cnn_score_workspace_bytes(13, 11, 7, 0) > L.sf_cnn_score_workspace_bytes(13, 0, 0, 0)
+    assert L.sf_cnn_score_workspace_bytes(13, 11, 7, 3) == L.sf_cnn_score_workspace_bytes(13, 0, 0, 3)    # (no sharing buffers)
     assert L.sf_cnn_score_rows(None, None, 4, 4, 0, 4, None, None, 8, 0, None, None, None, 0, None) == -1   # argument errors, no launch
 
 
