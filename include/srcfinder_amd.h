@@ -330,6 +330,13 @@ int sf_plumes_compact(int32_t *labels, int32_t *ncomp_dev, const uint8_t *ch4min
  * Deterministic: one workgroup per component sums its pixels in a fixed order.  ime = sum * ime_scale (:1989-1996). */
 int sf_plumes_stats(const int32_t *labels, const double *ch4mf, int H, int W, int ncomp, int32_t *irec, double *drec,
                     void *stream);
+/* Per-plume saliency (the reference's detection table columns salmax, salmaxrow, salmaxcol, salience_predictions.py:32): for
+ * every component 1..ncomp of labels, the largest value of the saliency map sal[H][W] over its pixels, skipping -9999 (CNN
+ * NODATA), -> smax[id], and the raster index of its first occurrence -> sidx[id]; a component without a scored pixel gets NaN and
+ * -1 (entry 0 too).  irec: the table sf_plumes_stats filled for these labels (its bounding boxes).  Deterministic: one workgroup
+ * per component, a fixed tree over (max, first index) pairs, as sf_plumes_stats. */
+int sf_plumes_saliency(const int32_t *labels, const float *sal, int H, int W, int ncomp, const int32_t *irec, float *smax,
+                       int32_t *sidx, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * CNN tile scorer (cnn/cnn_pred_pipeline.py + cnn/archs/googlenet1.py, eval graph).  Activations are NHWC
@@ -466,6 +473,19 @@ int sf_cnn_calibrate(const float *padded, int H, int W, const float *blob, int b
                      float *scales, void *stream);
 int sf_cnn_score_rows(const float *padded, const float *plane, int H, int W, int r0, int r1, const float *blob, float *out,
                       int batch, int route, const float *scales, int *info, void *workspace, size_t workspace_bytes, void *stream);
+/* The tile scorer on a SET of pixels (cnn_pred_pipeline.py:53-58, :173-189 on a subset of the items): scores the windows centred on
+ * the raster pixels pix[0 .. npix) (row * W + col; a DEVICE array of int64, any order, duplicates allowed) in batches of `batch` list
+ * entries and writes out[pix[i]] of the caller's H x W map (NODATA rule, plane, blob, scales as sf_cnn_score_rows); no other element
+ * of `out` is written.  Precondition: 0 <= pix[i] < H W.  Guard: a window whose index lies outside [0, H W) reads no part of the
+ * plane and writes nothing.  Routes 3, 4, 2, 1 (every window on its own; a window's bits do not depend on its batch, so the values
+ * equal sf_cnn_score_rows' on those pixels bit for bit unless either call scored a batch again); the sharing routes 0 / 5 return -1
+ * (route 3 is their bit-identical unshared form).  Scales, per-batch overflow slots and the re-scoring on route 4 as
+ * sf_cnn_score_rows (the same loop): info[0] the batches scored again, info[1] = 0; the split route synchronises `stream`.
+ * workspace >= sf_cnn_score_workspace_bytes(batch, 0, 0, route) (-4 otherwise).  Argument errors (-1) return before any HIP call;
+ * npix == 0 returns 0. */
+int sf_cnn_score_pixels(const float *padded, const float *plane, int H, int W, const long long *pix, long long npix,
+                        const float *blob, float *out, int batch, int route, const float *scales, int *info, void *workspace,
+                        size_t workspace_bytes, void *stream);
 
 /* Trunk sharing (csrc/cnn_share.hip, csrc/cnn_ring.h): cnn_pred_pipeline.py:53-58 scores one 256 x 256 window per pixel, so
  * neighbouring windows overlap by 255/256.  A layer's activation for one window lives on a G x G grid and depends on the window only

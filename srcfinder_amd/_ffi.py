@@ -69,6 +69,7 @@ SIGNATURES = {
     "sf_cnn_blob_floats": (sz, []),
     "sf_cnn_score_workspace_bytes": (C.c_size_t, [i32, i32, i32, i32]),
     "sf_cnn_score_rows": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, sz, vp]),
+    "sf_cnn_score_pixels": (i32, [vp, vp, i32, i32, vp, i64, vp, vp, i32, i32, vp, vp, vp, sz, vp]),
     "sf_cnn_fcn_prepare": (i32, [vp, i32, i32, f32, f32, f32, f32, i32, i32, i32, i32, i32, vp, vp]),
     "sf_cnn_conv1_image": (i32, [vp, i32, i32, i32, vp, vp, vp, i32, vp]),
     "sf_cnn_fcn_stitch": (i32, [vp, i32, i32, i32, i32, i32, vp, i32, i32, f32, vp, vp]),
@@ -112,6 +113,7 @@ SIGNATURES = {
     "sf_plumes_compact_scratch_bytes": (sz, [i32, i32]),
     "sf_plumes_compact": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, vp]),
     "sf_plumes_stats": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
+    "sf_plumes_saliency": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "sf_cmf_score_timing": (i32, [i32]),
     "sf_debug_set": (i32, [i32, i32]),
     "sf_debug_get": (i32, [i32, C.POINTER(C.c_int)]),

@@ -2,10 +2,13 @@
 """Command line of the CNN saliency scorer with the flag set of ``cnn/cnn_pred_pipeline.py:63-83``:
 
     python -m srcfinder_amd.cli_cnn_pred FLIGHTLINE [-m MODEL] [-g GPU ...] [-b BATCH] [-o OUTDIR] [--band N] [--weights PT]
+                                         [--mask IMG]
 
 FLIGHTLINE is an ENVI raster; ``--band`` (1-based, default 1 like the reference's ``read(1)``) selects the plane that
 is scored -- pass 4 for the CMF band of a 4-band matched-filter product.  Weights default to
-``<package>/models/<MODEL>.pt``; a missing file exits with status 1 like the reference (:90-95).
+``<package>/models/<MODEL>.pt``; a missing file exits with status 1 like the reference (:90-95).  ``--mask IMG`` (a
+single-band ENVI image of the flightline's lines x samples, e.g. cli_filtdet's ``<stem>_ccomp``) scores only the pixels
+where it is > 0; the map is 0 elsewhere.
 """
 import argparse
 import os
@@ -26,6 +29,7 @@ def build_parser():
     parser.add_argument('--output', '-o', help="Output directory for generated saliency maps.", default=".", type=str)
     parser.add_argument('--band', help="1-based band of the raster to score (reference: 1).", default=1, type=int)
     parser.add_argument('--weights', help="GoogLeNet state_dict (.pt); default <package>/models/<model>.pt", default=None)
+    parser.add_argument('--mask', help="single-band ENVI image (lines x samples): score only its pixels > 0", default=None)
     return parser
 
 
@@ -53,6 +57,15 @@ def main(argv=None):
     mm, meta = envi.open_memmap(args.flightline)
     bil = envi.to_bil(mm, meta)
     plane = np.ascontiguousarray(bil[:, args.band - 1, :], dtype=np.float32)
+    mask = None
+    if args.mask is not None:
+        mmask, mmeta = envi.open_memmap(args.mask)
+        mbil = envi.to_bil(mmask, mmeta)
+        if mbil.shape[1] != 1 or (mbil.shape[0], mbil.shape[2]) != plane.shape:
+            print("[ERR] --mask %s is %d x %d band(s) x %d: expected one band of %d x %d, exiting."
+                  % (args.mask, mbil.shape[0], mbil.shape[1], mbil.shape[2], plane.shape[0], plane.shape[1]))
+            return 1
+        mask = np.asarray(mbil[:, 0, :]) > 0
     print("[STEP] MODEL PREDICTION")
     # -g 0 1 2 3: every listed GPU scores its own block of rows with the per-GPU batch size (the reference multiplies
     # the batch by the GPU count for DataParallel to split again, cnn_pred_pipeline.py:170)
@@ -61,7 +74,7 @@ def main(argv=None):
     # at 32, 103-108 k at 1024 on an MI355X (the per-window rings of the shared trunk are small GEMMs) -- so at least 1024 windows are
     # scored per launch set (two concurrent row halves with 19 GB of workspace each per device)
     exec_batch = max(int(args.batch), 1024)
-    sal = cnn.predict_flightline(plane, args.model, weights=sd, batch=exec_batch, gpus=list(args.gpus), to_numpy=True)
+    sal = cnn.predict_flightline(plane, args.model, weights=sd, batch=exec_batch, gpus=list(args.gpus), to_numpy=True, mask=mask)
     print("[STEP] RESULT EXPORT")
     outpath = op.join(args.output, f"{Path(args.flightline).stem}_saliency.img")
     print("[INFO] Saving to", outpath)

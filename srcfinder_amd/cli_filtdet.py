@@ -3,12 +3,16 @@
 
     python -m srcfinder_amd.cli_filtdet CMF_IMG OUTDIR [--mfmin 500] [--mfmax 1500] [--minarea 9] [--kernel 50]
                                         [--mfminsmall 1250] [--use_abs] [--skip_kde] [--lid NAME]
+                                        [--weights PT [--model COVID_QC] [--batch 1024]]
 
 CMF_IMG is an ENVI matched-filter product (4 bands R, G, B, CMF; nodata where band 0 is -9999) or a single-band CMF
 image (nodata where it is -9999).  OUTDIR receives the three images ``filtdet`` can write -- ``<stem>_kde`` (the clipped
 KDE weighting before the ch4min / nodata zeroing; not with --skip_kde), ``<stem>_ccomp`` (components, -9999 on nodata)
 and ``<stem>_det`` (ch4mf, 0 below mfmin, -9999 on nodata) -- and ``<stem>_plumes.csv``, the plume table with the
-integrated mass enhancement of every component.
+integrated mass enhancement of every component.  With ``--weights`` (a GoogLeNet state_dict) the CNN scores the windows
+of the component pixels alone (``cnn.predict_flightline(mask=detcomp > 0)`` on the CMF band as float32): the table gains
+``salmax``, ``salmaxrow``, ``salmaxcol`` and ``<stem>_saliency`` is written (float32; 0 outside the components, -9999 on
+CNN NODATA).
 """
 import argparse
 import csv
@@ -31,6 +35,10 @@ def build_parser():
     p.add_argument("--use_abs", action="store_true", help="weight |ch4mf| instead of ch4mf")
     p.add_argument("--skip_kde", action="store_true", help="no KDE weighting")
     p.add_argument("--lid", default=None, help="line id of the plume ids (default: the image's stem)")
+    p.add_argument("--weights", default=None, help="GoogLeNet state_dict (.pt): score the component pixels with the CNN")
+    p.add_argument("--model", default="COVID_QC", choices=["COVID_QC", "CalCH4_v8", "Permian_QC", "multi_256", "multi_64"],
+                   help="normalisation of the CNN's input (with --weights)")
+    p.add_argument("--batch", type=int, default=1024, help="CNN windows per batch (with --weights)")
     return p
 
 
@@ -54,6 +62,9 @@ def main(argv=None):
         print("[ERR] no GPU visible: srcfinder_amd has no CPU path, exiting.")
         return 1
     from . import detections, envi, plumes
+    if args.weights is not None and not op.isfile(args.weights):
+        print("[ERR] weights %s not found, exiting." % args.weights)
+        return 1
     mm, meta = envi.open_memmap(args.cmf_img)
     bil = envi.to_bil(mm, meta)
     nb = bil.shape[1]
@@ -69,7 +80,12 @@ def main(argv=None):
     detkde, detcomp, kde_raw = plumes.filtdet(ch4mf, nodata, minarea=args.minarea, mfmin=args.mfmin, mfmax=args.mfmax,
                                               k=args.kernel, mfminsmall=args.mfminsmall, skip_kde=args.skip_kde,
                                               use_abs=args.use_abs, return_kde=True)
-    header, rows = plumes.plume_table(ch4mf, detcomp, mi, lid=lid)
+    sal = None
+    if args.weights is not None:                                                    # the CNN on the component pixels alone
+        from . import cnn
+        sd = torch.load(args.weights, map_location="cpu")
+        sal = cnn.predict_flightline(ch4mf.astype(np.float32), args.model, weights=sd, batch=args.batch, mask=detcomp > 0)
+    header, rows = plumes.plume_table(ch4mf, detcomp, mi, lid=lid, saliency=sal)
     comp = detcomp.cpu().numpy()
     if not args.skip_kde:                                                           # kde_outf (:1438-1439)
         _write(op.join(args.outdir, stem + "_kde"), meta, kde_raw.cpu().numpy(), np.float64)
@@ -80,11 +96,14 @@ def main(argv=None):
     det[ch4mf < args.mfmin] = 0
     det[nodata] = -9999
     _write(op.join(args.outdir, stem + "_det"), meta, det, np.float64)
+    if sal is not None:
+        _write(op.join(args.outdir, stem + "_saliency"), meta, sal.cpu().numpy(), np.float32)
     with open(op.join(args.outdir, stem + "_plumes.csv"), "w", newline="") as f:
         w = csv.writer(f)
         w.writerow(header)
         w.writerows(rows)
-    print("%d plumes, %.3f kg IME in all" % (len(rows), sum(r[-1] for r in rows)))
+    ime = header.index("ime_kg")
+    print("%d plumes, %.3f kg IME in all" % (len(rows), sum(r[ime] for r in rows)))
     return 0
 
 

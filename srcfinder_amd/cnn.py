@@ -606,6 +606,41 @@ def _score_rows_c(net, ds, r0, r1, batch, out, code, lanes=None):
     return nres[0]
 
 
+def _mask_pixels(mask, shape, device):
+    """The raster indices (int64 tensor on ``device``, ascending) of the True pixels of the [H, W] boolean ``mask`` (array or tensor,
+    host or device; a device mask on ``device`` stays there)."""
+    torch = _torch()
+    m = mask if torch.is_tensor(mask) else torch.as_tensor(np.asarray(mask))
+    if tuple(m.shape) != tuple(shape):
+        raise ValueError("mask shape %s differs from the plane's %s" % (tuple(m.shape), tuple(shape)))
+    if m.dtype != torch.bool:
+        raise ValueError("mask must be boolean, got %s" % (m.dtype,))
+    return torch.nonzero(m.reshape(-1)).reshape(-1).to(device)
+
+
+def _score_pixels_c(net, ds, pix, batch, out, code):
+    """ONE sf_cnn_score_pixels call on the windows at the raster pixels ``pix`` (int64 on the network's device) with the network's
+    current activation scales, on the calling thread's current stream; returns the batches re-scored."""
+    torch = _torch()
+    L = _ffi.lib()
+    H, W = ds.inshape[1], ds.inshape[2]
+    n = int(pix.numel())
+    net.last_batches, net.last_shared_batches = -(-n // int(batch)), 0
+    if n == 0:
+        return 0
+    with torch.cuda.device(net.device):
+        wsb = L.sf_cnn_score_workspace_bytes(int(batch), 0, 0, code)
+        ws = net._buf("c_driver_ws", ((wsb + 3) // 4,))
+        nres = (C.c_int * 2)(0, 0)
+        sc = (C.c_float * len(net.ascale))(*net.ascale)
+        _ffi.check(L.sf_cnn_score_pixels(_ffi.ptr(ds.x), _ffi.ptr(ds.plane), H, W, _ffi.ptr(pix), C.c_longlong(n),
+                                         _ffi.ptr(net.packed_blob()), _ffi.ptr(out), int(batch), code, sc, nres, _ffi.ptr(ws),
+                                         C.c_size_t(ws.numel() * 4), _ffi.stream_ptr()), "sf_cnn_score_pixels")
+    if nres[0]:
+        _overflow_warning("%d batch(es) of %d masked pixels" % (nres[0], n))
+    return int(nres[0])
+
+
 def score_tiles(net, ds, t_first, t_last, batch, out, route=None, lanes=None):
     """``net.forward_tiles`` over the windows [t_first, t_last) of the FlightlineConvolve ``ds`` in batches, asynchronously: on the
     split-operand route every batch raises its own overflow slot, the slots are read ONCE after the last batch and only the raised
@@ -623,7 +658,7 @@ def score_tiles(net, ds, t_first, t_last, batch, out, route=None, lanes=None):
 
 
 def predict_flightline(cmf2d, model="COVID_QC", weights=None, batch=32, gpus=None, rows=None, net=None, to_numpy=False,
-                       precision="fp32", route=None, info=None, scales=None, lanes=None):
+                       precision="fp32", route=None, info=None, scales=None, lanes=None, mask=None):
     """saliency[H, W] float32 = softmax(GoogLeNet(window))[:, 1] for the 256x256 window centred on every pixel,
     -9999 where ``cmf2d`` is -9999 (cnn_pred_pipeline.py:159-189).
 
@@ -633,6 +668,11 @@ def predict_flightline(cmf2d, model="COVID_QC", weights=None, batch=32, gpus=Non
               does: 20 k windows/s at the reference's default of 32, 100 k at 512, 103-108 k at 1024 on an MI355X (the CLI scores at
               least 1024 at a time)
     rows    : optional (r0, r1) image rows to score (multi-GPU row sharding); other rows are left at 0
+    mask    : optional [H, W] boolean array / tensor (host or device): only its pixels are scored (sf_cnn_score_pixels: every window on
+              its own), every other pixel is left at 0.  The values equal the full map's bit for bit unless either call scored a batch
+              again.  Routes None / "split" / "split_conv3" / "split_unshared" run as "split_unshared"; "winograd" / "direct" as
+              named.  Not with ``rows``, the fp16 network or ``net.c_driver = False``.  With ``gpus=[...]`` every device scores a
+              contiguous piece of the pixel list
     gpus    : device indices (the script's ``-g 0 1 2 3``, which wraps the model in ``DataParallel`` and re-scatters
               every batch, cnn_pred_pipeline.py:113-116).  Here every listed GPU gets its own copy of the weights and
               of the 69 MB padded plane and scores a contiguous block of image rows from its own host thread; the
@@ -648,11 +688,22 @@ def predict_flightline(cmf2d, model="COVID_QC", weights=None, batch=32, gpus=Non
               calibration on this plane (a campaign that wants ONE set of scales for all its flightlines; the tests)
     lanes   : concurrent parts of the row range on one device (default 2: two host threads, two HIP streams, two workspaces -- a
               second batch in flight fills the tails of the first one's small launches, +5-7 %; 1: one stream).  The map does not depend
-              on it unless a batch overflows float16: the re-scored batches are then cut at other windows
+              on it unless a batch overflows float16: the re-scored batches are then cut at other windows.  Not used with ``mask``
     info    : optional dict; receives ``rescued_batches``, ``shared_batches``, ``batches`` (launched by the C driver: the row range is
-              scored as two concurrent halves on two streams when it is long enough), ``route`` and the ``scales`` used
+              scored as two concurrent halves on two streams when it is long enough), ``route`` and the ``scales`` used; with ``mask``
+              ``rescued_batches``, ``batches``, ``route``, ``scales`` and ``pixels`` (the number scored)
     """
     torch = _torch()
+    if mask is not None:
+        if rows is not None:
+            raise ValueError("pass rows= or mask=, not both")
+        shape = tuple(cmf2d.shape)
+        if tuple(mask.shape) != shape:
+            raise ValueError("mask shape %s differs from the plane's %s" % (tuple(mask.shape), shape))
+        if precision == "fp16" or (net is not None and net.half):
+            raise ValueError("mask=: the fp16 network has no index-list scorer")
+        if net is not None and not net.c_driver:
+            raise ValueError("mask=: the Python-sequenced graph (net.c_driver = False) has no index-list scorer")
     if gpus is not None and len(gpus) > 0:
         gpus = [int(g) for g in gpus]
         if any(g < 0 for g in gpus):
@@ -662,7 +713,7 @@ def predict_flightline(cmf2d, model="COVID_QC", weights=None, batch=32, gpus=Non
         if len(gpus) > 1:
             if net is not None or rows is not None:
                 raise ValueError("gpus=[...] builds one network per device: do not pass net= or rows=")
-            return _predict_multi_gpu(cmf2d, model, weights, batch, gpus, to_numpy, precision, route, info, scales, lanes)
+            return _predict_multi_gpu(cmf2d, model, weights, batch, gpus, to_numpy, precision, route, info, scales, lanes, mask)
         if net is None:
             if weights is None:
                 raise ValueError("weights (a GoogLeNet state_dict) are required")
@@ -676,6 +727,9 @@ def predict_flightline(cmf2d, model="COVID_QC", weights=None, batch=32, gpus=Non
     out = torch.zeros(H * W, dtype=torch.float32, device=net.device)
     r0, r1 = (0, H) if rows is None else rows
     code = net._route_code(route)
+    if mask is not None and _shares(code):
+        code = ROUTES["split_unshared"]           # (a mask always runs unshared: the same bits)
+    pix = None if mask is None else _mask_pixels(mask, (H, W), net.device)
     rescued = 0
     if _splits(code, net.half):
         # ONE set of scales for the call, whichever driver sequences the graph: the caller's, or sf_cnn_calibrate on this plane
@@ -685,43 +739,68 @@ def predict_flightline(cmf2d, model="COVID_QC", weights=None, batch=32, gpus=Non
             net.ascale = [float(v) for v in scales]
         else:
             net.calibrate(ds, batch)
-    if not net.half and net.c_driver:
+    if pix is not None:
+        # the windows of the mask's pixels alone: one library call (per-batch overflow slots and the re-scoring included)
+        rescued = _score_pixels_c(net, ds, pix, batch, out, code)
+        if info is not None:
+            info.update(rescued_batches=rescued, route=code, scales=list(net.ascale) if _splits(code) else None,
+                        batches=net.last_batches, pixels=int(pix.numel()))
+    elif not net.half and net.c_driver:
         # the C-side driver sequences the whole graph for the row range: one library call (shared trunk, per-batch overflow slots
         # and the fp32 re-scoring of raised batches included)
         rescued = _score_rows_c(net, ds, r0, r1, batch, out, code, lanes) if r1 > r0 else 0
     else:
         rescued = score_tiles(net, ds, r0 * W, r1 * W, batch, out, route=code)
-    if info is not None:
+    if info is not None and pix is None:
         info.update(rescued_batches=rescued, route=code, scales=list(net.ascale) if _splits(code) else None,
                     shared_batches=net.last_shared_batches if _shares(code) else 0, batches=net.last_batches)
     out = out.view(H, W)
     return out.cpu().numpy() if to_numpy else out
 
 
-def _predict_multi_gpu(cmf2d, model, weights, batch, gpus, to_numpy, precision, route=None, info=None, scales=None, lanes=None):
-    """Row blocks of the saliency map on several GPUs of one process (one host thread per device)."""
+def _predict_multi_gpu(cmf2d, model, weights, batch, gpus, to_numpy, precision, route=None, info=None, scales=None, lanes=None,
+                       mask=None):
+    """Row blocks of the saliency map on several GPUs of one process (one host thread per device); with ``mask``, contiguous pieces of
+    its pixel list (raster order), each scored as a mask of its own and assembled on the first device."""
     torch = _torch()
     if weights is None:
         raise ValueError("weights (a GoogLeNet state_dict) are required")
     plane = cmf2d.detach().cpu().numpy() if torch.is_tensor(cmf2d) else np.asarray(cmf2d, dtype=np.float32)
-    H = plane.shape[0]
+    H, W = plane.shape
     n = len(gpus)
     parts, infos = [None] * n, [dict() for _ in range(n)]
     route = _route_code(route, precision == "fp16")       # (resolved HERE, once, and passed to every worker as an argument)
+    pix = None if mask is None else _mask_pixels(mask, (H, W), "cpu").numpy()      # (cut into the devices' pieces on the host)
+    pieces = None if pix is None else [pix[len(pix) * i // n:len(pix) * (i + 1) // n] for i in range(n)]
 
     def work(i):
         dev = torch.device("cuda", gpus[i])
         with torch.cuda.device(dev):
             net = GoogLeNetHIP(weights, device=dev, precision=precision)
+            if pieces is not None:
+                m = np.zeros(H * W, dtype=bool)
+                m[pieces[i]] = True
+                sal = predict_flightline(plane, model, net=net, batch=batch, route=route, info=infos[i], scales=scales,
+                                         mask=m.reshape(H, W))
+                parts[i] = sal.reshape(-1)[torch.as_tensor(pieces[i], device=dev)].to(torch.device("cuda", gpus[0]))
+                return
             r0, r1 = i * H // n, (i + 1) * H // n
             sal = predict_flightline(plane, model, net=net, batch=batch, rows=(r0, r1), route=route, info=infos[i], scales=scales,
                                      lanes=lanes)
             parts[i] = sal[r0:r1].to(torch.device("cuda", gpus[0]), non_blocking=False)
     _on_threads(n, work)
     if info is not None:
-        info.update(rescued_batches=sum(d.get("rescued_batches", 0) for d in infos), route=route,
+        info.update(rescued_batches=sum(d.get("rescued_batches", 0) for d in infos), route=infos[0].get("route", route),
                     per_block_rescued=[d.get("rescued_batches", 0) for d in infos], scales=infos[0].get("scales"))
-    out = torch.cat(parts, 0)
+        if pix is not None:
+            info.update(pixels=int(len(pix)), batches=sum(d.get("batches", 0) for d in infos))
+    if pix is None:
+        out = torch.cat(parts, 0)
+    else:
+        dev0 = torch.device("cuda", gpus[0])
+        out = torch.zeros(H * W, dtype=torch.float32, device=dev0)
+        out[torch.as_tensor(pix, device=dev0)] = torch.cat(parts, 0)
+        out = out.view(H, W)
     return out.cpu().numpy() if to_numpy else out
 
 

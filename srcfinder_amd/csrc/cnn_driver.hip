@@ -286,10 +286,12 @@ constexpr Route ROUTE[] = {{2, true, Form::Split}, {0, false, Form::Direct}, {0,
                            {0, true, Form::Split}, {0, false, Form::Wino},   {1, true, Form::Split}};   // split_unshared, winograd, split_conv3
 const Route *route_of(int code) { return code >= 0 && code < int(sizeof ROUTE / sizeof *ROUTE) ? ROUTE + code : nullptr; }
 
-// One batch of windows through the eval graph (googlenet1.py:110-163).  Split forms: `as` the NSCALE activation scales, `flag` the
-// batch's overflow slot.  amax != nullptr (Wino / Direct): the largest magnitude of every tensor a split convolution reads -> amax[NSCALE]
-int run_batch(Net &N, const float *padded, const float *plane, int H, int W, long long tile0, int n, Form form, const float *as, int *flag,
-              float *amax, float *out) {
+// One batch of windows through the eval graph (googlenet1.py:110-163): the windows at pixels tile0 .. tile0 + n - 1, or with an index
+// list (pix != nullptr; unshared forms only) at pixels pix[tile0 .. tile0 + n) -- only conv1 + maxpool1 and the head see where a window
+// lies.  Split forms: `as` the NSCALE activation scales, `flag` the batch's overflow slot.  amax != nullptr (Wino / Direct): the largest
+// magnitude of every tensor a split convolution reads -> amax[NSCALE]
+int run_batch(Net &N, const float *padded, const float *plane, int H, int W, long long tile0, const long long *pix, int n, Form form,
+              const float *as, int *flag, float *amax, float *out) {
   const int Hp = H + 255, Wp = W + 255;
   const bool share = form == Form::Shared;
   const bool use_split = share || form == Form::Split, use_wino = form == Form::Wino;
@@ -405,7 +407,9 @@ int run_batch(Net &N, const float *padded, const float *plane, int H, int W, lon
     }
   } else {
   // conv1 + maxpool1 (googlenet1.py:60-61), conv2, conv3, maxpool2 (:62-64)
-  if ((rc = sf_cnn_conv1_pool(padded, Hp, Wp, W, tile0, n, W_(N.L.conv1), B_(N.L.conv1), N.pool1, stream))) return rc;
+  if ((rc = pix ? sfi_cnn_conv1_pool_idx(padded, Hp, Wp, W, pix + tile0, n, W_(N.L.conv1), B_(N.L.conv1), N.pool1, stream)
+                : sf_cnn_conv1_pool(padded, Hp, Wp, W, tile0, n, W_(N.L.conv1), B_(N.L.conv1), N.pool1, stream)))
+    return rc;
   if ((rc = peak(N.pool1, (size_t)n * 64 * 64 * 64, 0))) return rc;
   if (use_split)
     rc = sf_cnn_conv_split(N.pool1, 0, n, 64, 64, 64, 64, N.shalf + N.SL.conv2.h, half_lo(N, N.SL.conv2, 64, 1, 64), N.sscale + N.SL.conv2.s,
@@ -474,6 +478,8 @@ int run_batch(Net &N, const float *padded, const float *plane, int H, int W, lon
     }
   }
   // global average pool, FC, softmax[:, 1], NODATA rule (:87-89; cnn_pred_pipeline.py:177-189)
+  if (out && pix)
+    return sfi_cnn_head_idx(x, n, hw * hw, cin, W_(N.L.fc), B_(N.L.fc), plane, pix + tile0, (long long)H * W, -9999.0f, out, stream);
   if (out) return sf_cnn_head(x, n, hw * hw, cin, W_(N.L.fc), B_(N.L.fc), plane, tile0, -9999.0f, out, stream);
   return 0;
 }
@@ -631,7 +637,7 @@ int calibrate(Net &N, const float *padded, int H, int W, int batch, float *scale
     last = t0;
     for (int k = 0; k < per; k += batch) {
       const int n = (per - k < batch) ? per - k : batch;
-      if ((rc = run_batch(N, padded, nullptr, H, W, t0 + k, n, Form::Wino, nullptr, nullptr, N.amax, nullptr))) return rc;
+      if ((rc = run_batch(N, padded, nullptr, H, W, t0 + k, nullptr, n, Form::Wino, nullptr, nullptr, N.amax, nullptr))) return rc;
     }
   }
   float mx[NSCALE];
@@ -648,6 +654,67 @@ int calibrate(Net &N, const float *padded, int H, int W, int batch, float *scale
     }
     scales[i] = s;
   }
+  return 0;
+}
+
+// THE batch / overflow-slot / rescue loop of both scoring entries, over the windows [i0, i1): pixels i0 .. i1 - 1 (pix == nullptr:
+// sf_cnn_score_rows' whole image rows, the trunk shared where the route and make_net built the maps) or the index-list entries
+// pix[i0 .. i1) (sf_cnn_score_pixels; unshared).  Split routes: the per-layer activation scales (the caller's, or calibrated on the
+// plane) against underflow; a batch that raised its overflow slot (read back every NFLAG batches) is scored again as Form::Wino
+// before the return, counted in info[0]; info[1] counts the batches on the shared trunk
+int score_windows(Net &N, const Route *R, const float *padded, const float *plane, int H, int W, long long i0, long long i1,
+                  const long long *pix, int batch, const float *scales, int *info, float *out, const char *who) {
+  int rc = 0;
+  auto unsplit = [&](long long t0, Form form) {       // one batch without scales or overflow slot (the other routes; the rescue)
+    return run_batch(N, padded, plane, H, W, t0, pix, (int)(i1 - t0 < batch ? i1 - t0 : batch), form, nullptr, nullptr, nullptr, out);
+  };
+  if (!R->split) {
+    if (R->form == Form::Wino && (rc = prepare_wino(N))) return rc;
+    for (long long tile0 = i0; tile0 < i1 && !rc; tile0 += batch) rc = unsplit(tile0, R->form);
+    return rc;
+  }
+  float as[NSCALE];
+  if (scales) {
+    for (int i = 0; i < NSCALE; ++i) {
+      int e;
+      if (!(scales[i] > 0.f && scales[i] < 3.0e38f && frexpf(scales[i], &e) == 0.5f)) {
+        sf_set_error("%s: scales[%d] is not a power of two", who, i);
+        return -1;
+      }
+      as[i] = scales[i];
+    }
+  } else if ((rc = calibrate(N, padded, H, W, batch, as))) return rc;
+  if ((rc = prepare_split(N))) return rc;
+  int host_flags[NFLAG];
+  long long group0 = i0;
+  while (group0 < i1) {
+    SF_HIP(hipMemsetAsync(N.flags, 0, NFLAG * sizeof(int), N.st));
+    int nb = 0;
+    long long tile0 = group0;
+    for (; tile0 < i1 && nb < NFLAG; tile0 += batch, ++nb) {
+      const int n = (int)((i1 - tile0 < batch) ? (i1 - tile0) : batch);
+      Form form = R->form;
+      if (N.share) {                           // the phase maps must cover the batch's image rows
+        const int rf = (int)(tile0 / W), rl = (int)((tile0 + n - 1) / W);
+        if (!(N.map_r0 >= 0 && N.map_r0 <= rf && rl < N.map_r1))
+          if ((rc = build_maps(N, padded, H, W, rf, as))) return rc;
+        if (N.map_ok) form = Form::Shared;
+        if (N.map_ok && info) ++info[1];
+        if (N.map_ok && N.SH.band && sf_tune().cnn_variant != 3 && !(N.strip_r0 >= 0 && N.strip_r0 <= rf && rl < N.strip_r0 + N.strip_nr))
+          if ((rc = build_strips(N, padded, H, W, rf, as))) return rc;
+      }
+      if ((rc = run_batch(N, padded, plane, H, W, tile0, pix, n, form, as, N.flags + nb, nullptr, out))) return rc;
+    }
+    SF_HIP(hipMemcpyAsync(host_flags, N.flags, nb * sizeof(int), hipMemcpyDeviceToHost, N.st));
+    SF_HIP(hipStreamSynchronize(N.st));
+    for (int b = 0; b < nb; ++b) {
+      if (!host_flags[b]) continue;
+      if ((rc = prepare_wino(N)) || (rc = unsplit(group0 + (long long)b * batch, Form::Wino))) return rc;
+      if (info) ++info[0];
+    }
+    group0 = tile0;
+  }
+  SF_HIP(hipStreamSynchronize(N.st));
   return 0;
 }
 
@@ -695,60 +762,31 @@ int sf_cnn_score_rows(const float *padded, const float *plane, int H, int W, int
   Net N = make_net(blob, batch, workspace, stream, H, W, R->depth, r0, r1, workspace_bytes);     // (depth 0: no sharing buffers)
   const long long i0 = (long long)r0 * W, i1 = (long long)r1 * W;
   if (i0 >= i1) return 0;
-  int rc = 0;
-  auto unsplit = [&](long long t0, Form form) {       // one batch without scales or overflow slot (the other routes; the rescue)
-    return run_batch(N, padded, plane, H, W, t0, (int)(i1 - t0 < batch ? i1 - t0 : batch), form, nullptr, nullptr, nullptr, out);
-  };
-  if (!R->split) {
-    if (R->form == Form::Wino && (rc = prepare_wino(N))) return rc;
-    for (long long tile0 = i0; tile0 < i1 && !rc; tile0 += batch) rc = unsplit(tile0, R->form);
-    return rc;
+  return score_windows(N, R, padded, plane, H, W, i0, i1, nullptr, batch, scales, info, out, "sf_cnn_score_rows");
+}
+
+int sf_cnn_score_pixels(const float *padded, const float *plane, int H, int W, const long long *pix, long long npix, const float *blob,
+                        float *out, int batch, int route, const float *scales, int *info, void *workspace, size_t workspace_bytes,
+                        void *stream) {
+  const Route *R = route_of(route);
+  if (!padded || !pix || !blob || !out || !workspace || H < 1 || W < 1 || npix < 0 || batch < 1 || !R) {
+    sf_set_error("sf_cnn_score_pixels: bad argument");
+    return -1;
   }
-  // the split-operand routes' range contracts: the per-layer activation scales (the caller's, or calibrated on the plane) against
-  // underflow; a batch that raised its overflow slot (read back every NFLAG batches) is scored again as Form::Wino before the return
-  float as[NSCALE];
-  if (scales) {
-    for (int i = 0; i < NSCALE; ++i) {
-      int e;
-      if (!(scales[i] > 0.f && scales[i] < 3.0e38f && frexpf(scales[i], &e) == 0.5f)) {
-        sf_set_error("sf_cnn_score_rows: scales[%d] is not a power of two", i);
-        return -1;
-      }
-      as[i] = scales[i];
-    }
-  } else if ((rc = calibrate(N, padded, H, W, batch, as))) return rc;
-  if ((rc = prepare_split(N))) return rc;
-  int host_flags[NFLAG];
-  long long group0 = i0;
-  while (group0 < i1) {
-    SF_HIP(hipMemsetAsync(N.flags, 0, NFLAG * sizeof(int), N.st));
-    int nb = 0;
-    long long tile0 = group0;
-    for (; tile0 < i1 && nb < NFLAG; tile0 += batch, ++nb) {
-      const int n = (int)((i1 - tile0 < batch) ? (i1 - tile0) : batch);
-      Form form = R->form;
-      if (N.share) {                           // the phase maps must cover the batch's image rows
-        const int rf = (int)(tile0 / W), rl = (int)((tile0 + n - 1) / W);
-        if (!(N.map_r0 >= 0 && N.map_r0 <= rf && rl < N.map_r1))
-          if ((rc = build_maps(N, padded, H, W, rf, as))) return rc;
-        if (N.map_ok) form = Form::Shared;
-        if (N.map_ok && info) ++info[1];
-        if (N.map_ok && N.SH.band && sf_tune().cnn_variant != 3 && !(N.strip_r0 >= 0 && N.strip_r0 <= rf && rl < N.strip_r0 + N.strip_nr))
-          if ((rc = build_strips(N, padded, H, W, rf, as))) return rc;
-      }
-      if ((rc = run_batch(N, padded, plane, H, W, tile0, n, form, as, N.flags + nb, nullptr, out))) return rc;
-    }
-    SF_HIP(hipMemcpyAsync(host_flags, N.flags, nb * sizeof(int), hipMemcpyDeviceToHost, N.st));
-    SF_HIP(hipStreamSynchronize(N.st));
-    for (int b = 0; b < nb; ++b) {
-      if (!host_flags[b]) continue;
-      if ((rc = prepare_wino(N)) || (rc = unsplit(group0 + (long long)b * batch, Form::Wino))) return rc;
-      if (info) ++info[0];
-    }
-    group0 = tile0;
+  if (R->depth) {
+    sf_set_error("sf_cnn_score_pixels: route %d shares the trunk between neighbouring windows of image rows; pass route 3, its "
+                 "bit-identical form with every window on its own", route);
+    return -1;
   }
-  SF_HIP(hipStreamSynchronize(N.st));
-  return 0;
+  const size_t need = sf_cnn_score_workspace_bytes(batch, 0, 0, route);
+  if (workspace_bytes < need) {
+    sf_set_error("sf_cnn_score_pixels: workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    return -4;
+  }
+  if (info) info[0] = info[1] = 0;          // [0] batches scored again on the fp32 matrix cores, [1] 0 (no trunk sharing)
+  if (npix == 0) return 0;
+  Net N = make_net(blob, batch, workspace, stream);
+  return score_windows(N, R, padded, plane, H, W, 0, npix, pix, batch, scales, info, out, "sf_cnn_score_pixels");
 }
 #undef W_
 #undef B_

@@ -1,7 +1,16 @@
 // Entry points between the tile scorer's translation units that are NOT part of the C ABI (hidden visibility): the side-row forms of
-// the ring kernels that the band-sharing driver (cnn_driver.hip, round 6) sequences.  Geometry: cnn_ring.h.
+// the ring kernels that the band-sharing driver (cnn_driver.hip, round 6) sequences (geometry: cnn_ring.h), and the index-list forms
+// of the two position-dependent kernels that sf_cnn_score_pixels sequences.
 #pragma once
 #include <cstddef>
+
+// sf_cnn_conv1_pool / sf_cnn_head with window t of the batch taken at raster pixel pix[t] (device array, ntiles entries) instead of
+// tile0 + t.  Guard: an index outside [0, H W) (H = Hp - 255; npx = H W for the head) reads no patch (its pool1 output is that of a
+// window of zeros) and writes no output.
+int sfi_cnn_conv1_pool_idx(const float *padded, int Hp, int Wp, int W, const long long *pix, int ntiles, const float *w,
+                           const float *bias, float *out, void *stream);
+int sfi_cnn_head_idx(const float *in, int ntiles, int HW, int C, const float *fcw, const float *fcb, const float *plane,
+                     const long long *pix, long long npx, float nodata, float *out, void *stream);
 
 // sf_cnn_conv_ring with the rows restricted to the SIDE positions of the output frame (G (olo + ohi) per window); row (window, j) is
 // written to row window * count(G, olo, ohi) + its ring index of out0 / out1 / out2 -- the full ring tensors, whose band interior

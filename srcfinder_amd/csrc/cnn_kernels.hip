@@ -5,6 +5,7 @@
 // channel slice of the concatenated output.  Convolutions run as implicit GEMM on the fp32 matrix cores
 // (v_mfma_f32_32x32x2_f32: exact fp32 FMA chains, no reduced precision) -- MFMA-bound: 3.7 GFLOP per tile.
 #include "cmf_common.h"
+#include "cnn_internal.h"
 
 typedef float f16_t __attribute__((ext_vector_type(16)));
 typedef unsigned u4_t __attribute__((ext_vector_type(4)));
@@ -95,6 +96,7 @@ static size_t cp_lds_bytes() { return ((size_t)CP_PATCH * CP_LDP + CP_KP * CP_LD
 // 4 no matrix loop, 8 no conv-tile store, 16 no pooling reads, 32 no global store
 template <int EXP>
 __global__ __launch_bounds__(256, 2) void k_conv1_pool(const float *__restrict__ padded, int Wp, int Wimg, long long tile0,
+                                                        const long long *__restrict__ pix, long long npx,
                                                         const float *__restrict__ w /*[64][49]*/, const float *__restrict__ bias,
                                                         float *__restrict__ out /*[n][64][64][64]*/) {
   extern __shared__ __attribute__((aligned(16))) float cp_lds[];
@@ -104,7 +106,8 @@ __global__ __launch_bounds__(256, 2) void k_conv1_pool(const float *__restrict__
   float *bs = convt + CP_NPX * CP_LDC;                     // [64]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int t = blockIdx.y;
-  const long long tile = tile0 + t;
+  const long long tile = pix ? pix[t] : tile0 + t;
+  const bool inside = (unsigned long long)tile < (unsigned long long)npx;         // (an index outside the plane reads nothing)
   const int trow = (int)(tile / Wimg), tcol = (int)(tile % Wimg);
   const int py0 = (blockIdx.x >> 3) * CP_PT, px0 = (blockIdx.x & 7) * CP_PT;     // pooled block origin
   const int cy0 = 2 * py0, cx0 = 2 * px0;                                         // conv block origin
@@ -117,7 +120,7 @@ __global__ __launch_bounds__(256, 2) void k_conv1_pool(const float *__restrict__
     const int py = i / CP_PATCH, px = i % CP_PATCH;
     const int iy = 2 * cy0 - 3 + py, ix = 2 * cx0 - 3 + px;                      // tile-local input coordinates
     float v = 0.f;                                                               // the tile is its own image: zero outside
-    if (iy >= 0 && iy < 256 && ix >= 0 && ix < 256 && !(EXP & 2)) v = padded[(size_t)(trow + iy) * Wp + tcol + ix];
+    if (inside && iy >= 0 && iy < 256 && ix >= 0 && ix < 256 && !(EXP & 2)) v = padded[(size_t)(trow + iy) * Wp + tcol + ix];
     patch[py * CP_LDP + px] = v;
   }
   __syncthreads();
@@ -199,6 +202,7 @@ constexpr int C2_NT = 512, C2_NW = C2_NT / 64, C2_PASS = 3;
 static size_t c2_lds_bytes() { return ((size_t)C2_PATCH * C2_LDP + CP_KP * CP_LDB + (size_t)C2_PT * C2_PT * 32 + 64) * sizeof(float); }
 template <int EXP>
 __global__ __launch_bounds__(C2_NT, 2) void k_conv1_pool16(const float *__restrict__ padded, int Wp, int Wimg, long long tile0,
+                                                            const long long *__restrict__ pix, long long npx,
                                                             const float *__restrict__ w /*[64][49]*/,
                                                             const float *__restrict__ bias,
                                                             float *__restrict__ out /*[n][64][64][64]*/) {
@@ -209,7 +213,8 @@ __global__ __launch_bounds__(C2_NT, 2) void k_conv1_pool16(const float *__restri
   float *bs = reinterpret_cast<float *>(pooled + C2_PT * C2_PT * 32);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int t = blockIdx.y;
-  const long long tile = tile0 + t;
+  const long long tile = pix ? pix[t] : tile0 + t;
+  const bool inside = (unsigned long long)tile < (unsigned long long)npx;         // (an index outside the plane reads nothing)
   const int trow = (int)(tile / Wimg), tcol = (int)(tile % Wimg);
   const int py0 = (blockIdx.x >> 2) * C2_PT, px0 = (blockIdx.x & 3) * C2_PT;      // pooled block origin
   const int cy0 = 2 * py0, cx0 = 2 * px0;                                         // conv block origin
@@ -222,7 +227,7 @@ __global__ __launch_bounds__(C2_NT, 2) void k_conv1_pool16(const float *__restri
     const int py = i / C2_PATCH, px = i % C2_PATCH;
     const int iy = 2 * cy0 - 3 + py, ix = 2 * cx0 - 3 + px;                      // tile-local input coordinates
     float v = 0.f;                                                               // the tile is its own image: zero outside
-    if (iy >= 0 && iy < 256 && ix >= 0 && ix < 256) v = padded[(size_t)(trow + iy) * Wp + tcol + ix];
+    if (inside && iy >= 0 && iy < 256 && ix >= 0 && ix < 256) v = padded[(size_t)(trow + iy) * Wp + tcol + ix];
     patch[py * C2_LDP + px] = v;
   }
   const int l31 = lane & 31, kh = lane >> 5;
@@ -763,9 +768,11 @@ static int launch_poolconv(const float *in, int M, int H, int W, int Cin, const 
 
 // ---- head: global average pool -> FC(1024 -> 2) -> softmax[:,1]; NODATA where the input plane is NODATA ------------
 // (googlenet1.py:87-89,:156-161; cnn_pred_pipeline.py:177-189)
+// Window t is pixel tile0 + t, or pix[t] for an index list; a pixel outside [0, npx) is not written.
 __global__ __launch_bounds__(256) void k_head(const float *__restrict__ in, int HW, int C, const float *__restrict__ fcw,
                                                const float *__restrict__ fcb, const float *__restrict__ plane, long long tile0,
-                                               float nodata, float *__restrict__ out) {
+                                               const long long *__restrict__ pix, long long npx, float nodata,
+                                               float *__restrict__ out) {
   __shared__ float red[2][256];
   const int t = blockIdx.x, tid = threadIdx.x;
   float d0 = 0.f, d1 = 0.f;
@@ -798,8 +805,11 @@ __global__ __launch_bounds__(256) void k_head(const float *__restrict__ in, int 
     const float mx = fmaxf(l0, l1);
     const float e0 = expf(l0 - mx), e1 = expf(l1 - mx);
     float p = e1 / (e0 + e1);
-    if (plane && plane[tile0 + t] == nodata) p = nodata;
-    out[tile0 + t] = p;
+    const long long tile = pix ? pix[t] : tile0 + t;
+    if ((unsigned long long)tile < (unsigned long long)npx) {
+      if (plane && plane[tile] == nodata) p = nodata;
+      out[tile] = p;
+    }
   }
 }
 
@@ -843,7 +853,46 @@ static int conv_dispatch(const float *in, int N, int H, int W, int Cin, int ld_i
 #undef SF_CONV
 }
 
+// the launches of the two position-dependent kernels: windows tile0 .. tile0 + ntiles - 1 (pix == nullptr), or pix[0 .. ntiles) (the
+// sfi_ forms; an index outside the plane's Hp - 255 rows x W pixels is neither read nor written)
+int launch_conv1_pool(const float *padded, int Hp, int Wp, int W, long long tile0, const long long *pix, int ntiles, const float *w,
+                      const float *bias, float *out, void *stream) {
+  const long long npx = (long long)(Hp - 255) * W;
+  if (sf_tune().cnn_variant == 1) {                  // the 8 x 8 form with the conv tile in LDS
+    if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_conv1_pool<0>), cp_lds_bytes())) return rc;
+    hipLaunchKernelGGL(k_conv1_pool<0>, dim3(64, ntiles), dim3(256), cp_lds_bytes(), (hipStream_t)stream, padded, Wp, W, tile0, pix,
+                       npx, w, bias, out);
+  } else {
+    if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_conv1_pool16<0>), c2_lds_bytes())) return rc;
+    hipLaunchKernelGGL(k_conv1_pool16<0>, dim3(16, ntiles), dim3(C2_NT), c2_lds_bytes(), (hipStream_t)stream, padded, Wp, W, tile0,
+                       pix, npx, w, bias, out);
+  }
+  SF_LAUNCH_CHECK("k_conv1_pool");
+  return 0;
+}
+int launch_head(const float *in, int ntiles, int HW, int C, const float *fcw, const float *fcb, const float *plane, long long tile0,
+                const long long *pix, long long npx, float nodata, float *out, void *stream) {
+  hipLaunchKernelGGL(k_head, dim3(ntiles), dim3(256), 0, (hipStream_t)stream, in, HW, C, fcw, fcb, plane, tile0, pix, npx, nodata,
+                     out);
+  SF_LAUNCH_CHECK("k_head");
+  return 0;
+}
+
 }  // namespace
+
+int sfi_cnn_conv1_pool_idx(const float *padded, int Hp, int Wp, int W, const long long *pix, int ntiles, const float *w,
+                           const float *bias, float *out, void *stream) {
+  if (!padded || !pix || !w || !bias || !out || ntiles < 1 || W < 1 || Wp != W + 255 || Hp < 256) {
+    sf_set_error("sfi_cnn_conv1_pool_idx: bad argument");
+    return -1;
+  }
+  return launch_conv1_pool(padded, Hp, Wp, W, 0, pix, ntiles, w, bias, out, stream);
+}
+int sfi_cnn_head_idx(const float *in, int ntiles, int HW, int C, const float *fcw, const float *fcb, const float *plane,
+                     const long long *pix, long long npx, float nodata, float *out, void *stream) {
+  if (!in || !fcw || !fcb || !pix || !out || ntiles < 1 || npx < 1) { sf_set_error("sfi_cnn_head_idx: bad argument"); return -1; }
+  return launch_head(in, ntiles, HW, C, fcw, fcb, plane, 0, pix, npx, nodata, out, stream);
+}
 
 extern "C" {
 
@@ -879,17 +928,7 @@ int sf_cnn_conv1_pool(const float *padded, int Hp, int Wp, int W, long long tile
     sf_set_error("sf_cnn_conv1_pool: bad argument");
     return -1;
   }
-  if (sf_tune().cnn_variant == 1) {                  // the 8 x 8 form with the conv tile in LDS
-    if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_conv1_pool<0>), cp_lds_bytes())) return rc;
-    hipLaunchKernelGGL(k_conv1_pool<0>, dim3(64, ntiles), dim3(256), cp_lds_bytes(), (hipStream_t)stream, padded, Wp, W, tile0, w,
-                       bias, out);
-  } else {
-    if (int rc = sf_lds_attr(reinterpret_cast<const void *>(k_conv1_pool16<0>), c2_lds_bytes())) return rc;
-    hipLaunchKernelGGL(k_conv1_pool16<0>, dim3(16, ntiles), dim3(C2_NT), c2_lds_bytes(), (hipStream_t)stream, padded, Wp, W, tile0,
-                       w, bias, out);
-  }
-  SF_LAUNCH_CHECK("k_conv1_pool");
-  return 0;
+  return launch_conv1_pool(padded, Hp, Wp, W, tile0, nullptr, ntiles, w, bias, out, stream);
 }
 
 int sf_cnn_maxpool(const float *in, int N, int H, int W, int C, int ksize, int stride, int pad, float *out, int Ho,
@@ -977,10 +1016,7 @@ int sf_cnn_conv_split3(const float *in, int N, int H, int W, int Cin, int ld_in,
 int sf_cnn_head(const float *in, int ntiles, int HW, int C, const float *fcw, const float *fcb, const float *plane,
                 long long tile0, float nodata, float *out, void *stream) {
   if (!in || !fcw || !fcb || !out || ntiles < 1) { sf_set_error("sf_cnn_head: bad argument"); return -1; }
-  hipLaunchKernelGGL(k_head, dim3(ntiles), dim3(256), 0, (hipStream_t)stream, in, HW, C, fcw, fcb, plane, tile0, nodata,
-                     out);
-  SF_LAUNCH_CHECK("k_head");
-  return 0;
+  return launch_head(in, ntiles, HW, C, fcw, fcb, plane, tile0, nullptr, tile0 + ntiles, nodata, out, stream);
 }
 
 }  // extern "C"

@@ -313,6 +313,11 @@ __global__ __launch_bounds__(256) void k_ptab_bbox(const int32_t *__restrict__ l
   atomicAdd(&r[0], 1);
   atomicMin(&r[1], y); atomicMax(&r[2], y + 1); atomicMin(&r[3], x); atomicMax(&r[4], x + 1);
 }
+// the (max, first raster index) pair of two: the larger value, on a tie the earlier index
+template <typename T>
+__device__ inline void keep_first_max(T &m, long long &i, T m2, long long i2) {
+  if (m2 > m || (m2 == m && i2 < i)) { m = m2; i = i2; }
+}
 // one workgroup per component over its bounding box: thread t takes the box's pixels t, t + 256, ... in raster order,
 // then a fixed tree combines the 256 partial sums and the (max, first raster index) pairs
 __global__ __launch_bounds__(256) void k_ptab_stats(const int32_t *__restrict__ labels, const double *__restrict__ ch4mf,
@@ -338,9 +343,7 @@ __global__ __launch_bounds__(256) void k_ptab_stats(const int32_t *__restrict__ 
   for (int o = 128; o > 0; o >>= 1) {
     if (tid < o) {
       ssum[tid] += ssum[tid + o];
-      const double m2 = smax[tid + o];
-      const long long i2 = sidx[tid + o];
-      if (m2 > smax[tid] || (m2 == smax[tid] && i2 < sidx[tid])) { smax[tid] = m2; sidx[tid] = i2; }
+      keep_first_max(smax[tid], sidx[tid], smax[tid + o], sidx[tid + o]);
     }
     __syncthreads();
   }
@@ -348,6 +351,40 @@ __global__ __launch_bounds__(256) void k_ptab_stats(const int32_t *__restrict__ 
     drec[(size_t)id * 2] = ssum[0];
     drec[(size_t)id * 2 + 1] = smax[0];
     if (bn > 0) { r[5] = (int)(sidx[0] / W); r[6] = (int)(sidx[0] % W); }
+  }
+}
+
+// the per-plume saliency: k_ptab_stats' walk and tree over the saliency map, pixels at -9999 (CNN NODATA) skipped; workgroup 0 writes
+// the unused entry 0.  A component without a scored pixel: NaN, -1
+__global__ __launch_bounds__(256) void k_ptab_saliency(const int32_t *__restrict__ labels, const float *__restrict__ sal, int W,
+                                                        const int32_t *__restrict__ irec, float *__restrict__ smax,
+                                                        int32_t *__restrict__ sidx) {
+  __shared__ float sm[256];
+  __shared__ long long si[256];
+  const int id = blockIdx.x, tid = threadIdx.x;
+  const int32_t *r = irec + (size_t)id * 8;
+  const int y0 = r[1], x0 = r[3], bw = r[4] - r[3];
+  const long long bn = (id > 0 && r[0] > 0) ? (long long)(r[2] - r[1]) * bw : 0;
+  constexpr long long NONE = 0x7fffffffffffffffll;
+  float m = -__builtin_inff();
+  long long mi = NONE;
+  for (long long k = tid; k < bn; k += 256) {
+    const size_t i = (size_t)(y0 + k / bw) * W + (size_t)(x0 + k % bw);
+    if (labels[i] == id) {
+      const float v = sal[i];
+      if (v != -9999.0f && v > m) { m = v; mi = (long long)i; }      // first in raster order: strict >
+    }
+  }
+  sm[tid] = m; si[tid] = mi;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) keep_first_max(sm[tid], si[tid], sm[tid + o], si[tid + o]);
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const bool any = si[0] != NONE;
+    smax[id] = any ? sm[0] : __builtin_nanf("");
+    sidx[id] = any ? (int32_t)si[0] : -1;
   }
 }
 
@@ -486,6 +523,17 @@ int sf_plumes_stats(const int32_t *labels, const double *ch4mf, int H, int W, in
   SF_LAUNCH_CHECK("k_ptab_bbox");
   hipLaunchKernelGGL(k_ptab_stats, dim3(ncomp), dim3(256), 0, st, labels, ch4mf, W, irec, drec);
   SF_LAUNCH_CHECK("k_ptab_stats");
+  return 0;
+}
+
+int sf_plumes_saliency(const int32_t *labels, const float *sal, int H, int W, int ncomp, const int32_t *irec, float *smax,
+                       int32_t *sidx, void *stream) {
+  if (!labels || !sal || !irec || !smax || !sidx || !plane_ok(H, W) || ncomp < 0) {
+    sf_set_error("sf_plumes_saliency: bad argument");
+    return -1;
+  }
+  hipLaunchKernelGGL(k_ptab_saliency, dim3(ncomp + 1), dim3(256), 0, (hipStream_t)stream, labels, sal, W, irec, smax, sidx);
+  SF_LAUNCH_CHECK("k_ptab_saliency");
   return 0;
 }
 

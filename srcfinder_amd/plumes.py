@@ -24,6 +24,8 @@ NODATA = -9999
 
 HEADER = ["plumeid", "lid", "npix", "bbminr", "bbmaxr", "bbminc", "bbmaxc",
           "ppmmmax", "ppmmmaxrow", "ppmmmaxcol", "ppmmmaxlat", "ppmmmaxlon", "ppmmsum", "ime_kg"]
+# plume_table(..., saliency=): the CNN saliency per plume, named as in the reference's detection table (salience_predictions.py:32)
+SALIENCY_COLUMNS = ["salmax", "salmaxrow", "salmaxcol"]
 
 
 def ime_scale(ps):
@@ -139,12 +141,15 @@ def filtdet(ch4mf, nodata_mask, minarea=MINAREA, mfmin=MFMIN, mfmax=MFMAX, k=KER
     return detkde, labels
 
 
-def plume_table(ch4mf, detcomp, mapinfo=None, lid="", as_dataframe=False):
+def plume_table(ch4mf, detcomp, mapinfo=None, lid="", as_dataframe=False, saliency=None):
     """Per component 1..n of ``detcomp``: npix, bounding slices (row start, row stop, col start, col stop), the max ppm m
     with its first (row, col) in raster order and their lat/lon (``detections.sl2latlon``; NaN without ``mapinfo``),
     the sum of ppm m and ``ime_kg = sum * ime_scale(ps)`` with ``ps`` the map info's pixel size (``xps``; NaN without).
-    ``mapinfo``: a dict from ``detections.mapinfo`` or the header's ``map info``.  Returns ``(HEADER, rows)`` or a
-    DataFrame."""
+    ``mapinfo``: a dict from ``detections.mapinfo`` or the header's ``map info``.  ``saliency``: an optional [H, W] CNN
+    saliency map (e.g. ``cnn.predict_flightline(..., mask=detcomp > 0)``); each row then ends with ``salmax``, ``salmaxrow``,
+    ``salmaxcol`` -- the largest saliency over the component's pixels that are not -9999 and its first (row, col) in raster
+    order (NaN, -1, -1 when it has none).  Returns ``(header, rows)`` (header = HEADER, + SALIENCY_COLUMNS with ``saliency``)
+    or a DataFrame."""
     import torch
     from . import detections
     if not torch.cuda.is_available():
@@ -153,6 +158,8 @@ def plume_table(ch4mf, detcomp, mapinfo=None, lid="", as_dataframe=False):
         raise ValueError("ch4mf %s and detcomp %s must be the same 2-d shape" % (tuple(ch4mf.shape), tuple(detcomp.shape)))
     if mapinfo is not None and not isinstance(mapinfo, dict):
         mapinfo = detections.mapinfo(mapinfo)
+    if saliency is not None and tuple(saliency.shape) != tuple(detcomp.shape):
+        raise ValueError("saliency %s and detcomp %s must be the same shape" % (tuple(saliency.shape), tuple(detcomp.shape)))
     x = _to_device(ch4mf, torch.float64)
     lab = _to_device(detcomp, torch.int32)
     H, W = x.shape
@@ -163,6 +170,12 @@ def plume_table(ch4mf, detcomp, mapinfo=None, lid="", as_dataframe=False):
         irec = torch.empty((n + 1, 8), dtype=torch.int32, device=x.device)
         drec = torch.zeros((n + 1, 2), dtype=torch.float64, device=x.device)
         _ffi.check(L.sf_plumes_stats(P(lab), P(x), H, W, n, P(irec), P(drec), st()), "sf_plumes_stats")
+        if saliency is not None:
+            sal = _to_device(saliency, torch.float32).to(x.device)
+            smax = torch.empty(n + 1, dtype=torch.float32, device=x.device)
+            sidx = torch.empty(n + 1, dtype=torch.int32, device=x.device)
+            _ffi.check(L.sf_plumes_saliency(P(lab), P(sal), H, W, n, P(irec), P(smax), P(sidx), st()), "sf_plumes_saliency")
+            smax, sidx = smax.cpu().numpy()[1:], sidx.cpu().numpy()[1:]
         irec = irec.cpu().numpy()[1:]
         drec = drec.cpu().numpy()[1:]
     ps = float(mapinfo["xps"]) if mapinfo is not None and mapinfo.get("xps") is not None else float("nan")
@@ -180,10 +193,14 @@ def plume_table(ch4mf, detcomp, mapinfo=None, lid="", as_dataframe=False):
         s, m = float(drec[i, 0]), float(drec[i, 1])
         rows.append(["%s-%d" % (lid, i + 1) if lid else str(i + 1), lid, npix, r0, r1, c0, c1, m, mr, mc, lat, lon, s,
                      s * scale])
+        if saliency is not None:
+            k = int(sidx[i])
+            rows[-1] += [float(smax[i]), k // W if k >= 0 else -1, k % W if k >= 0 else -1]
+    header = HEADER + SALIENCY_COLUMNS if saliency is not None else HEADER
     if not as_dataframe:
-        return HEADER, rows
+        return header, rows
     from pandas import DataFrame
-    return DataFrame.from_records(rows, columns=HEADER)
+    return DataFrame.from_records(rows, columns=header)
 
 
 def detect_plumes(product_out, mapinfo=None, lid="", **kw):

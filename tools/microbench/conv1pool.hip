@@ -11,10 +11,10 @@ float run(const float *padded, int Wp, int W, int ntiles, const float *w, const 
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_conv1_pool<EXP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)cp_lds_bytes());
   hipEvent_t e0, e1;
   (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-  hipLaunchKernelGGL(k_conv1_pool<EXP>, dim3(64, ntiles), dim3(256), cp_lds_bytes(), 0, padded, Wp, W, 0ll, w, b, out);
+  hipLaunchKernelGGL(k_conv1_pool<EXP>, dim3(64, ntiles), dim3(256), cp_lds_bytes(), 0, padded, Wp, W, 0ll, (const long long *)nullptr, (long long)ntiles, w, b, out);
   (void)hipEventRecord(e0);
   for (int r = 0; r < 3; ++r)
-    hipLaunchKernelGGL(k_conv1_pool<EXP>, dim3(64, ntiles), dim3(256), cp_lds_bytes(), 0, padded, Wp, W, 0ll, w, b, out);
+    hipLaunchKernelGGL(k_conv1_pool<EXP>, dim3(64, ntiles), dim3(256), cp_lds_bytes(), 0, padded, Wp, W, 0ll, (const long long *)nullptr, (long long)ntiles, w, b, out);
   (void)hipEventRecord(e1);
   (void)hipEventSynchronize(e1);
   float ms;
@@ -28,10 +28,10 @@ float run16(const float *padded, int Wp, int W, int ntiles, const float *w, cons
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_conv1_pool16<EXP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c2_lds_bytes());
   hipEvent_t e0, e1;
   (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-  hipLaunchKernelGGL(k_conv1_pool16<EXP>, dim3(16, ntiles), dim3(C2_NT), c2_lds_bytes(), 0, padded, Wp, W, 0ll, w, b, out);
+  hipLaunchKernelGGL(k_conv1_pool16<EXP>, dim3(16, ntiles), dim3(C2_NT), c2_lds_bytes(), 0, padded, Wp, W, 0ll, (const long long *)nullptr, (long long)ntiles, w, b, out);
   (void)hipEventRecord(e0);
   for (int r = 0; r < 3; ++r)
-    hipLaunchKernelGGL(k_conv1_pool16<EXP>, dim3(16, ntiles), dim3(C2_NT), c2_lds_bytes(), 0, padded, Wp, W, 0ll, w, b, out);
+    hipLaunchKernelGGL(k_conv1_pool16<EXP>, dim3(16, ntiles), dim3(C2_NT), c2_lds_bytes(), 0, padded, Wp, W, 0ll, (const long long *)nullptr, (long long)ntiles, w, b, out);
   (void)hipEventRecord(e1);
   (void)hipEventSynchronize(e1);
   float ms;
