@@ -1,14 +1,17 @@
 #!/usr/bin/env python3
 """Headline benchmark: columnwise matched filter (CMF) Mpixels/s on a 598 x 20000 x 425 float32 BIL cube.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W             # the headline alone: set-up, warm-up, the K timed steps, the line
+    python bench.py --gpus 1 --steps K --warmup W --full      # + every other section of the line (minutes)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A step = one full pass of the hot path (extract -> mean -> covariance -> eigh -> LOO sweep -> filter -> score)
 over the whole flightline, cube resident in HBM, outputs left on the device.  With N > 1 the cross-track
 columns are sharded contiguously over the ranks (each rank holds only its own column slice of the cube) and
 the step ends with ONE RCCL gather of the score blocks to rank 0 -- total work is fixed: "strong" scaling.
-Rank 0 prints one JSON line (see DESIGN.md §Measurement for every field).
+Rank 0 prints one JSON line (see DESIGN.md §Measurement for every field).  A plain run measures the headline and nothing else;
+--full adds the one-in-flight pass with the score kernel's roofline, the CPU baselines, the CNN / end-to-end / window /
+full-band / ingest / route sections and the traffic ceilings, each of which takes runs of its own.
 """
 import os
 
@@ -36,6 +39,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--lines", type=int, default=LINES)
     ap.add_argument("--samples", type=int, default=SAMPLES)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure every other section of the line as well: the one-in-flight pass and the score "
+                         "kernel's roofline, CPU baselines, CNN, end to end, the other windows, full band, ingest, sweep routes, "
+                         "traffic ceilings (minutes; the --no-* options below switch single sections of it off)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-cnn", action="store_true", help="skip the CNN tile-scorer section of the line (BASELINE configs 4/5)")
     ap.add_argument("--cnn-tiles", type=int, default=16384)
@@ -240,21 +247,18 @@ def main():
     main = timed_pass(depth)
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, main["res"], main["gathered"] if world > 1 or force_dist else None)
-    solo = main if depth == 1 else timed_pass(1)
-    res = solo["res"]
+    # --full: the same K steps once more with ONE flightline in flight (a pass of its own).  A run at depth 1 is that pass already.
+    solo = main if depth == 1 else timed_pass(1) if args.full else None
 
     if rank == 0:
         ms_per_step = main["dt"] / args.steps * 1e3
         mpix = lines * samples / (main["dt"] / args.steps) / 1e6
-        score_ms = solo["score_ms"]
-        npix = lines * ncols
-        # SURVEY.md §8(d): algorithmic bytes of the score kernel = every active value once (4p B) + one float64 score
-        # (8 B) per pixel; every pixel counts (a NODATA row has to be read to be recognised and its record is written).
-        # The kernel also copies the three RGB bands into the 32-byte BIP record (12 B read + 24 B written per pixel):
-        # that is real traffic of this fused launch but NOT part of §8(d)'s figure -- reported as `frac_with_fused_rgb`.
-        alg_bytes = (4 * p + 8) * npix
-        achieved = alg_bytes / (score_ms * 1e-3) / 1e9 if score_ms > 0 else 0.0
-        fused_bytes = (4 * p + 12 + 32) * npix
+        placement = {"three_in_flight": main["placement"]}
+        if solo is not None:
+            placement["one_in_flight"] = solo["placement"]
+        placement["note"] = ("FlightlinePipeline.pick_product_buffers (library API, set-up, untimed): score-kernel "
+                             "ms of one flightline into each candidate product buffer; the fastest are "
+                             "kept (profiles/r05_score_placement.md)")
         line = {
             "metric": "CMF Mpixels/s on 598x20000x425 cube",
             "value": round(mpix, 3), "unit": "Mpixel/s", "n_gpus": world, "steps": args.steps,
@@ -268,26 +272,38 @@ def main():
                        "in_flight": "%d flightlines in flight per GPU (one HIP stream each); the same depth for every N"
                                     % depth,
                        "gather_verified": main["gather_verified"],
-                       "product_buffer_placement": {"three_in_flight": main["placement"], "one_in_flight": solo["placement"],
-                                                    "note": "FlightlinePipeline.pick_product_buffers (library API, set-up, untimed): score-kernel "
-                                                            "ms of one flightline into each candidate product buffer; the fastest are "
-                                                            "kept (profiles/r05_score_placement.md)"},
+                       "product_buffer_placement": placement,
                        "host_enqueue_ms_per_step": round(main["t_enq"] / args.steps * 1e3, 3),
-                       "one_in_flight": {"ms_per_step": round(solo["dt"] / args.steps * 1e3, 3),
-                                         "value": round(lines * samples / (solo["dt"] / args.steps) / 1e6, 3),
-                                         "note": "the same K steps with ONE flightline in flight (latency of a flightline)"},
                        "output": "float64 BIP [lines, samples, (R,G,B,CMF)]"},
-            "roofline": {"bound": "hbm", "kernel": "k_score<RGB> (64-sample blocks, staged stores)", "achieved": round(achieved, 1),
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                         "traffic": None, "bytes_per_pixel": 4 * p + 8,
-                         "algorithmic_bytes_per_launch": alg_bytes,
-                         "frac_with_fused_rgb": round(fused_bytes / (score_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-                         if score_ms > 0 else 0.0,
-                         "avg_launch_ms": round(score_ms, 4), "launches": solo["launches"],
-                         "measured": "HIP events on the launch stream around the kernel alone, one flightline in flight"},
+            "sections": "all (--full)" if args.full else "headline only (--full measures the rest)",
         }
+    if rank == 0 and solo is not None:
+        res = solo["res"]
+        score_ms = solo["score_ms"]
+        npix = lines * ncols
+        # SURVEY.md §8(d): algorithmic bytes of the score kernel = every active value once (4p B) + one float64 score
+        # (8 B) per pixel; every pixel counts (a NODATA row has to be read to be recognised and its record is written).
+        # The kernel also copies the three RGB bands into the 32-byte BIP record (12 B read + 24 B written per pixel):
+        # that is real traffic of this fused launch but NOT part of §8(d)'s figure -- reported as `frac_with_fused_rgb`.
+        alg_bytes = (4 * p + 8) * npix
+        achieved = alg_bytes / (score_ms * 1e-3) / 1e9 if score_ms > 0 else 0.0
+        fused_bytes = (4 * p + 12 + 32) * npix
+        line["config"]["one_in_flight"] = {"ms_per_step": round(solo["dt"] / args.steps * 1e3, 3),
+                                           "value": round(lines * samples / (solo["dt"] / args.steps) / 1e6, 3),
+                                           "note": "the same K steps with ONE flightline in flight (latency of a flightline)"}
+        line["roofline"] = {"bound": "hbm", "kernel": "k_score<RGB> (64-sample blocks, staged stores)", "achieved": round(achieved, 1),
+                            "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                            "traffic": None, "bytes_per_pixel": 4 * p + 8,
+                            "algorithmic_bytes_per_launch": alg_bytes,
+                            "frac_with_fused_rgb": round(fused_bytes / (score_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+                            if score_ms > 0 else 0.0,
+                            "avg_launch_ms": round(score_ms, 4), "launches": solo["launches"],
+                            "measured": "HIP events on the launch stream around the kernel alone, one flightline in flight"}
         line["roofline"].update(pmc_traffic(lines, samples, p, world))
-        if world == 1 and (lines, samples, p) == (LINES, SAMPLES, 72) and not args.no_ceiling and not under_profiler():
+    if rank == 0 and args.full:
+        # every section below takes runs (or host minutes) of its own
+        fullsize = world == 1 and (lines, samples, p) == (LINES, SAMPLES, 72)
+        if fullsize and not args.no_ceiling and not under_profiler():
             line["roofline"].update(measured_ceiling(score_ms))
             line["roofline"].update(in_step_traffic(cube, lib, (a0, a1)))
         if world == 1 and not args.no_cpu_baseline:
@@ -296,21 +312,20 @@ def main():
             # the second half of the path (BASELINE.json configs 4 / 5): the per-pixel GoogLeNet tile scorer on the CMF plane
             # this run produced -- its own metric (tiles/s) and its own roofline (fp32 MFMA), inside the same line
             line["cnn"] = cnn_section(res, args.cnn_tiles, args.cnn_batch, not args.no_cpu_baseline)
-        full = world == 1 and (lines, samples, p) == (LINES, SAMPLES, 72)
-        if full and not args.no_routes:
+        if fullsize and not args.no_routes:
             # which sweep kernel each column took (the step's cost depends on it) and the same step on a hard spectrum
             line["sweep_routes"] = cmf.sweep_routes(cube, lib, active=(a0, a1))
             line["hard_spectrum"] = hard_spectrum_section(cube, lib, (a0, a1), depth)
-        if full and not args.no_windows:
+        if fullsize and not args.no_windows:
             # the reference's other two windows (cmf/robust_mf.py:186-191): CO2 radiance 309..391 (p = 83) at the headline's
             # depth, and the -R reflectance window 5..420 (p = 416, the wide route) one flightline at a time
             line["co2"] = window_section(cube, lib, cmf.active_window("co2", False), False, depth, 10, ms_per_step)
-        if full and not args.no_ingest:
+        if fullsize and not args.no_ingest:
             line["ingest"] = ingest_section(cube, lib, res)
-        if full and not args.no_e2e:
+        if fullsize and not args.no_e2e:
             # BASELINE config 4 made visible to the driver: cube -> CMF -> saliency map of the WHOLE flightline
             line["e2e"] = e2e_section(cube, lib, solo["dt"] / args.steps, line.get("cnn"))
-        if full and not args.no_wide:
+        if fullsize and not args.no_wide:
             # SURVEY 8(d) lists the full-band window among the configs: the batched-GEMM path, bounded to three flightlines
             del main, solo
             if not args.no_windows:

@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp
 for rep in 1 2; do
 for lib in "$@"; do
   cp $root/$lib $root/srcfinder_amd/libsrcfinder_amd.so
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ab_$rep -o p -- python3 $root/bench.py --no-cpu-baseline --steps 10 > /tmp/ab.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ab_$rep -o p -- python3 $root/bench.py --full --no-cpu-baseline --steps 10 > /tmp/ab.log 2>&1
   f=$(find /tmp/ab_$rep -name "*kernel_stats.csv" | head -1)
   echo "$lib: $(python3 -c "
 import csv,sys

@@ -18,8 +18,8 @@ tools/prof_bench.sh ${tag}fif1 --in-flight 1 --steps 5 --warmup 2 $B > $out/prof
 grep "^{\"metric\"" gpurun_out/prof_${tag}fif1.log | tail -1 > $out/bench_line_inflight1_rocprof.json
 cp gpurun_out/${tag}fif1_kstats.txt $out/kstats_inflight1.txt
 rm -rf gpurun_out/prof_${tag}fif1 gpurun_out/pmc_${tag}f_FETCH_SIZE gpurun_out/pmc_${tag}f_WRITE_SIZE gpurun_out/pmc_mfma_${tag}f gpurun_out/pmc_sq_${tag}f
-python bench.py > $out/bench_line.json 2> $out/bench_line.err
-python bench.py --samples 75 --no-cnn > $out/bench_line_shard75.json 2> /dev/null
+python bench.py --full > $out/bench_line.json 2> $out/bench_line.err
+python bench.py --full --samples 75 --no-cnn > $out/bench_line_shard75.json 2> /dev/null
 python bench.py --samples 75 --no-cnn --in-flight 1 --no-cpu-baseline > $out/bench_line_shard75_inflight1.json 2> /dev/null
 # a failed step must not reach profiles/: every record has to be what it claims to be (ADVICE r2 / VERDICT r3 item 9)
 for j in $out/bench_line.json $out/bench_line_shard75.json $out/bench_line_shard75_inflight1.json $out/bench_line_inflight1_rocprof.json; do
